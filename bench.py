@@ -8,8 +8,18 @@ already resident in HBM (generated on the device before the timed region).  Each
 dense 2^16-row x 256-weight gate table (64 MiB), so S streams use S x 64.5 MiB of HBM.
 
   python bench.py [--gpus N --steps K --warmup W] [--streams S --bits T --config single|synth3|stock]
+                  [--dump-outputs DIR] [--full]
 
-The same JSON line carries, under "also", the other shapes the north_star names, each timed the same
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, and the one
+JSON line (contract fields, the timed launches' roofline).  --dump-outputs DIR then also writes what the
+last timed step computed -- every stream's probability of every bit, p[stream][bit] as the caller of the
+path receives it -- to DIR/p.npy (float32; above 64 MB a fixed, seeded sample of streams, DIR/p_sample.npy,
+with their indices in DIR/p_streams.npy).  The records are generated from fixed seeds, so the same
+arguments give the same inputs on every run and two builds can be compared output for output.
+
+--full adds everything else the bench measures: the one-core reference figure ("cpu_baseline"), each
+timed launch once more under its own HIP events (kernel_ms_min/median/max), the committed PMC traffic
+of the same launch shape, and under "also" the other shapes the north_star names, each timed the same
 way (barrier, K steps, max over ranks) with its own roofline and one-core reference figure:
   synth3       256 inputs x 24/8/1 mixers (configs[2]'s shape), new gate rows every bit
   stock_held   the reference's own 90 inputs x 24/8/1, gate contexts held through a byte
@@ -29,7 +39,8 @@ way (barrier, K steps, max over ranks) with its own roofline and one-core refere
                coded bit for all of them -- scripts/bench_e2e.py measure_decode()
 The e2e_* values are COLD (whole process, exec to exit, Predictor construction included) like the reference CLI they
 are set against.  "fracs" (top level, before "also") repeats every kernel's roofline fraction in one short object.
-(--no-also leaves them out; --config X makes X the headline workload for profiling.)
+(With --full, --no-also and --no-cpu-baseline leave those parts out again; --config X makes X the headline
+workload for profiling.)
 
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks come from the environment;
 started plainly (`python bench.py --gpus N`, WORLD_SIZE unset) this process touches neither torch nor
@@ -37,7 +48,8 @@ HIP and starts torch.distributed.run itself as a child, relaying rank 0's line a
 Streams shard across ranks with no data-path collective (weak scaling: S streams per GPU); the only
 communication is the barrier, a MAX all-reduce of the elapsed time and a SUM of the stream counts.
 
-Prints ONE JSON line (rank 0) with the contract's fields plus "roofline", "cpu_baseline", "also".
+Prints ONE JSON line (rank 0) with the contract's fields plus "roofline" (and, with --full, "cpu_baseline"
+and "also").
 """
 import argparse
 import json
@@ -75,6 +87,23 @@ WORKLOADS = {
                   "configs[1] for ONE stream: synthetic 256-input 1-layer mixer, random logits, forward+update"),
 }
 ALSO = ("synth3", "stock_held", "stock_real", "stock_fresh", "stock_S1", "single_S1")
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, p):
+    """p[stream][bit] of the last timed step into out_dir/p.npy (float32); when that would pass DUMP_BYTES,
+    a fixed, seeded sample of whole streams into p_sample.npy and their indices into p_streams.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    p = np.ascontiguousarray(p, np.float32)
+    if p.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "p.npy"), p)
+        return
+    S, T = p.shape
+    n = max(1, min(S, DUMP_BYTES // (4 * T)))
+    rows = np.sort(np.random.default_rng(0).choice(S, n, replace=False))
+    np.save(os.path.join(out_dir, "p_sample.npy"), np.ascontiguousarray(p[rows, :DUMP_BYTES // 4]))
+    np.save(os.path.join(out_dir, "p_streams.npy"), rows.astype(np.float64))
 
 
 def aux_bench(script):
@@ -198,8 +227,11 @@ class Comm:
 
 
 def run_workload(name, comm, local_rank, streams=None, bits=None, steps=None, warmup=2, ring_n=4,
-                 ctx_mode=None, ctx_mod=1, stock_pairs=False, variant=0, want_cpu=True, cpu_sample_bits=None):
-    """Time K steps of one workload on this rank's GPU; rank 0 gets the result dict."""
+                 ctx_mode=None, ctx_mod=1, stock_pairs=False, variant=0, want_cpu=True, cpu_sample_bits=None,
+                 full=True, dump_dir=None):
+    """Time K steps of one workload on this rank's GPU; rank 0 gets the result dict.  full=False leaves out
+    what takes runs of its own (per-launch events, PMC summary lookup); dump_dir: rank 0 writes the last
+    timed step's probabilities there."""
     import gmix_amd
     kind, mode0, S0, T0, total, sample0, workload = WORKLOADS[name]
     topo = make_topology(kind)
@@ -246,9 +278,16 @@ def run_workload(name, comm, local_rank, streams=None, bits=None, steps=None, wa
     elapsed = comm.max(mine)
     S_all = comm.sum(S)  # a rank with less free HBM runs fewer streams
     rank_rates = comm.gather(S * T * steps / mine)  # every rank's own bits/s (its clock ends at the common barrier)
-    # the same launches once more, each bracketed by its own HIP events (outside the timed region: bracketing
-    # synchronises): how much a step varies
-    each = sorted(g.run(ring[k % len(ring)], T, learn=True, timed=True) for k in range(min(steps, 8)))
+    if dump_dir and comm.rank == 0:
+        last = ring[(steps - 1) % len(ring)]   # nothing has run on it since the last timed step
+        last.download(T)
+        last.wait()
+        dump_outputs(dump_dir, last.p[:, :T])
+    each = None
+    if full:
+        # the same launches once more, each bracketed by its own HIP events (outside the timed region: bracketing
+        # synchronises): how much a step varies
+        each = sorted(g.run(ring[k % len(ring)], T, learn=True, timed=True) for k in range(min(steps, 8)))
     bank_bytes = g.bank_bytes
     build = g.L.gmx_build_info().decode()
     for b in ring:
@@ -280,14 +319,16 @@ def run_workload(name, comm, local_rank, streams=None, bits=None, steps=None, wa
                    "parallelism": f"streams sharded over {comm.n_gpus} GPU(s), no collective on the data path"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": kernel, "kernel_ms_avg": avg_ms,
-                     "kernel_ms_min": each[0], "kernel_ms_median": each[len(each) // 2], "kernel_ms_max": each[-1],
                      "algorithmic_bytes_per_bit": bytes_per_bit, "bytes_per_launch": bytes_per_launch,
                      "build": build},
     }
-    try:
-        out["roofline"].update(pmc_traffic(kernel, S, T, ctx_mode, build))
-    except Exception as e:
-        sys.stderr.write(f"[bench] no PMC summary: {e}\n")
+    if full:
+        out["roofline"].update({"kernel_ms_min": each[0], "kernel_ms_median": each[len(each) // 2],
+                                "kernel_ms_max": each[-1]})
+        try:
+            out["roofline"].update(pmc_traffic(kernel, S, T, ctx_mode, build))
+        except Exception as e:
+            sys.stderr.write(f"[bench] no PMC summary: {e}\n")
     if comm.n_gpus > 1:
         out["per_rank"] = {"bits_per_s": rank_rates, "min": min(rank_rates), "max": max(rank_rates),
                            "numa_pinned_cpus": comm.pinned}
@@ -333,6 +374,10 @@ def main():
     ap.add_argument("--ctx-mod", type=int, default=1)
     ap.add_argument("--stock-pairs", action="store_true",
                     help="--config stock*: the lane-pair kernel (gmx_wide.hip) instead of the generated streams")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's probabilities p[stream][bit] to DIR/p.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the one-core reference figure, per-launch timings, the PMC traffic and every also{} entry")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="only the headline workload")
     ap.add_argument("--only-also", default="", help="comma-separated: of the also{} entries, only these")
@@ -411,12 +456,13 @@ def main():
     section("setup")
     head = run_workload(args.config, comm, local_rank, streams=args.streams, bits=args.bits, steps=args.steps,
                         warmup=args.warmup, ring_n=args.ring, ctx_mode=args.ctx_mode, ctx_mod=args.ctx_mod,
-                        stock_pairs=args.stock_pairs, variant=args.variant, want_cpu=not args.no_cpu_baseline,
-                        cpu_sample_bits=args.cpu_sample_bits)
+                        stock_pairs=args.stock_pairs, variant=args.variant,
+                        want_cpu=args.full and not args.no_cpu_baseline, cpu_sample_bits=args.cpu_sample_bits,
+                        full=args.full, dump_dir=args.dump_outputs)
     section(args.config)
     also = {}
     only = {x for x in args.only_also.split(",") if x}
-    if not args.no_also:
+    if args.full and not args.no_also:
         for name in ALSO:
             if name == args.config or (only and name not in only):
                 continue

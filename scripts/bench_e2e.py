@@ -3,7 +3,7 @@
 the run-ahead compressor (gmix_amd/host/gmx_batched.h) taking the device-side models in batches -- BASELINE.json
 configs[2] / [3] in small, on text that is on both boxes (GMX_CORPUS=/path/to/enwik8 for the named data).
 
-  variant "mixers": the 33 mixers on the MI355X (dropin/_build/gmix_many); the host keeps all 88 feature models
+  variant "mixers": the 33 mixers on the MI355X (oracle/_ref/dropin/gmix_many); the host keeps all 88 feature models
   variant "chain":  LSTM + 41 Indirect models + 33 mixers on the MI355X (gmix_chain_many); the host keeps PPMd, the
                     match models, the context hashes and the coder
 
@@ -27,7 +27,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref")          # the checker: stock builds (cpu_baseline, identical_to_stock)
-DROPIN = os.path.join(ROOT, "dropin", "_build")     # the product inside the reference (dropin/Makefile)
+DROPIN = os.path.join(REF, "dropin")                # the product inside the reference (dropin/Makefile)
 EXE = {"mixers": "gmix_many", "chain": "gmix_chain_many"}
 
 

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 import corpus  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref")
-DROPIN = os.path.join(ROOT, "dropin", "_build")
+DROPIN = os.path.join(REF, "dropin")
 
 
 def md5(b):

@@ -10,12 +10,12 @@ echo "host: $(grep -m1 'model name' /proc/cpuinfo | cut -d: -f2), cpu.max $(cat 
 for S in $LIST; do
   rm -rf $W/f $W/c; mkdir -p $W/f
   for i in $(seq 0 $((S-1))); do python3 scripts/corpus.py $W/f/$(printf %04d $i) $N $((i*1531)) > /dev/null; done
-  dropin/_build/gmix_chain_many $W/c $W/f/* > /dev/null 2>&1
+  oracle/_ref/dropin/gmix_chain_many $W/c $W/f/* > /dev/null 2>&1
   C=$(for i in $(seq 0 $((S-1))); do echo $W/c/$i.gmix; done)
   for rep in 1 2; do
     for MODE in ${MODES:-narrow share node none}; do
       PIN=""; [ $MODE = none ] && PIN="--no-pin"
-      GMX_PIN_MODE=$MODE dropin/_build/gmix_chain_many -d --groups ${GROUPS_N:-1} $PIN $W/b $C > $W/j.json 2> $W/err
+      GMX_PIN_MODE=$MODE oracle/_ref/dropin/gmix_chain_many -d --groups ${GROUPS_N:-1} $PIN $W/b $C > $W/j.json 2> $W/err
       python3 -c "import json;j=json.load(open('$W/j.json'));print('S=%d %-6s: %6.1f us per step, %.3g bits/s in the loops, failed %d; whole process %.1f s wall, %.1f s of CPU, %d involuntary switches' % (j['files'], '$MODE', j['wall_seconds']*1e6/j['launches'], j['bits_per_second'], j['failed'], j['total_seconds'], j['cpu_seconds'], j['involuntary_switches']))"
     done
   done

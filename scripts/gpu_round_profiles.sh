@@ -1,13 +1,16 @@
 #!/bin/bash
 # Everything profiles/rNN_* is made from, in three GPU calls (each inside gpurun's 20 minutes):
-#   bash scripts/gpu_round_profiles.sh <round> a|b|c
+#   bash scripts/gpu_round_profiles.sh <round> a|b|c [bench line path, default build/bench_default]
+# (part a writes `bench.py --full`'s line to <path>.json and its stderr to <path>.err)
 # (summaries are produced afterwards, in the build container, by scripts/round_profiles_summary.sh)
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out
 PART=${2:-abc}
+BENCH_OUT=${3:-build/bench_default}
 if [[ $PART == *a* ]]; then
 S=$(date +%s)
-timeout -k 10 600 python3 bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; echo "bench rc $? in $(( $(date +%s) - S )) s"
+mkdir -p "$(dirname "$BENCH_OUT")"
+timeout -k 10 600 python3 bench.py --full > "$BENCH_OUT.json" 2> "$BENCH_OUT.err"; echo "bench rc $? in $(( $(date +%s) - S )) s"
 bash scripts/gpu_profile.sh bench_single --config single --steps 12
 bash scripts/gpu_profile.sh synth3 --config synth3 --steps 6
 bash scripts/gpu_profile.sh stock_held --config stock_held --steps 8

@@ -6,7 +6,7 @@ W=$(mktemp -d); mkdir $W/f
 cat DESIGN.md SURVEY.md INTEGRATION.md README.md DESIGN.md SURVEY.md INTEGRATION.md README.md > $W/corpus
 for i in $(seq 0 $((${3:-1}-1))); do tail -c +$((i*1531+1)) $W/corpus | head -c ${1:-20000} > $W/f/$i; done
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $W/prof -o run -- dropin/_build/gmix_chain_many -T ${2:-2048} $W/out $W/f/* > $W/j.json 2> $W/err
+rocprofv3 --kernel-trace --output-format csv -d $W/prof -o run -- oracle/_ref/dropin/gmix_chain_many -T ${2:-2048} $W/out $W/f/* > $W/j.json 2> $W/err
 f=$(find $W/prof -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

@@ -7,10 +7,10 @@ S=${1:-64}; N=${2:-1500}; OUT=${3:-gpurun_out/decode_step_S$S.txt}
 mkdir -p $(dirname $OUT)
 W=$(mktemp -d); mkdir $W/f
 for i in $(seq 0 $((S-1))); do python3 scripts/corpus.py $W/f/$(printf %04d $i) $N $((i*1531)) > /dev/null; done
-dropin/_build/gmix_chain_many $W/c $W/f/* > $W/c.json 2> $W/c.err || { echo "compress failed"; tail -3 $W/c.err; exit 1; }
+oracle/_ref/dropin/gmix_chain_many $W/c $W/f/* > $W/c.json 2> $W/c.err || { echo "compress failed"; tail -3 $W/c.err; exit 1; }
 export TMPDIR=/tmp
 # (keep S x bytes small: rocprofv3 7.2 segfaults past about 8 192 replayed graph kernel nodes, see trace_chainstep.sh)
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $W/prof -o run -- dropin/_build/gmix_chain_many -d $W/back $(for i in $(seq 0 $((S-1))); do echo $W/c/$i.gmix; done) > $W/j.json 2> $W/err
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $W/prof -o run -- oracle/_ref/dropin/gmix_chain_many -d $W/back $(for i in $(seq 0 $((S-1))); do echo $W/c/$i.gmix; done) > $W/j.json 2> $W/err
 python3 - $W/prof $W/j.json <<'PY' | tee $OUT
 import csv, glob, json, sys
 root, jf = sys.argv[1:3]

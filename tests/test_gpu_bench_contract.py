@@ -1,22 +1,59 @@
-"""bench.py's one JSON line: the driver's contract fields, `roofline`, `cpu_baseline`, and under `also`
-the north_star's other shapes -- on reduced sizes (headline launch, end-to-end files) so that the test
-takes a minute or two."""
+"""bench.py's one JSON line: the driver's contract fields and `roofline` of a plain run (and what it writes with
+--dump-outputs); with --full also `cpu_baseline` and under `also` the north_star's other shapes -- on reduced
+sizes (headline launch, end-to-end files) so that the test takes a minute or two."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_line_carries_the_contract(gpu):
+def _env():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--streams", "1024", "--bits", "256", "--steps", "4",
+    return env
+
+
+def _plain(dump_dir):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--streams", "256", "--bits", "512",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump_dir)],
+                       env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_bench_line_and_its_outputs(gpu, tmp_path):
+    """A plain run: the contract's fields, exactly --steps timed steps after --warmup, nothing of --full; and
+    --dump-outputs writes the last timed step's probabilities, the same on a second run with the same arguments."""
+    d = _plain(tmp_path / "a")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert d["unit"] == "bits/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 1
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["config"]["streams_per_gpu"] == 256
+    assert d["config"]["bits_per_step"] == 256 * 512 and d["config"]["total_bits"] == 3 * 256 * 512
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 256 * 512 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["roofline"]["kernel_ms_avg"] <= d["ms_per_step"] * 1.02
+    assert "cpu_baseline" not in d and "also" not in d and "kernel_ms_min" not in d["roofline"]
+    assert sorted(os.listdir(tmp_path / "a")) == ["p.npy"]
+    p = np.load(tmp_path / "a" / "p.npy")
+    assert p.dtype == np.float32 and p.shape == (256, 512)
+    assert np.all(np.isfinite(p)) and np.all((p > 0) & (p < 1)) and len(np.unique(p)) > 1000
+    _plain(tmp_path / "b")
+    assert np.array_equal(np.load(tmp_path / "b" / "p.npy").view(np.uint32), p.view(np.uint32))
+
+
+def test_bench_line_carries_the_contract(gpu):
+    env = _env()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--streams", "1024", "--bits", "256", "--steps", "4",
                         "--cpu-sample-bits", "100000", "--e2e-bytes", "3000", "--e2e-many-bytes", "3000", "--decode-bytes", "300",
                         "--decode-streams", "8", "--also-streams-div", "4"],
                        env=env, capture_output=True, text=True, timeout=900)

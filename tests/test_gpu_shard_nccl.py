@@ -82,7 +82,8 @@ def test_bench_whole_files_on_every_rank(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--streams", "256", "--bits", "128",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--only-also", "e2e_S64", "--e2e-many-bytes", "6000"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--only-also", "e2e_S64",
+                        "--e2e-many-bytes", "6000"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
