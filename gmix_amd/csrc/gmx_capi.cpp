@@ -41,6 +41,7 @@ hipError_t gmx_launch_bank_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* ar
                                   unsigned lds_bytes, int has_mask, int l0, int l1, int ns, int fin,
                                   unsigned stride0, hipStream_t stream);
 hipError_t gmx_bank_kernel_set_lds(unsigned lds_bytes);
+int gmx_bank_kernel_build(int l0, int l1, int ns, int fin, unsigned stride0);
 hipError_t gmx_launch_stock_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* args, int n_streams,
                                    unsigned lds_bytes, int has_mask, int staged, int pow2_tables, hipStream_t stream);
 hipError_t gmx_launch_single_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* args, int n_inputs,
@@ -1550,6 +1551,17 @@ extern "C" int gmx_debug_force_general(gmx_group* g, int on) {
   if (!g) return GMX_ERR_INVALID;
   g->force_general = on != 0;
   return GMX_OK;
+}
+
+// The kernel a batched launch of `mode` (GMX_MODE_* bits) takes: kernel_for()'s kind (0 single, 1 wide, 2 stock,
+// 3 bank) plus, for the bank kernel, 4 x the build gmx_pick_bank_kernel takes (0 run-time, 1 unrolled 24/8/1 with
+// stride0 65..128, 2 unrolled 24/8/1 with stride0 257..512).  Tests assert their route with it.
+extern "C" int gmx_debug_kernel_kind(gmx_group* g, unsigned mode) {
+  if (!g) return GMX_ERR_INVALID;
+  const GmxKernelKind kind = kernel_for(g, mode);
+  if (kind != GMX_K_BANK) return (int)kind;
+  const GmxTopoDev& t = g->topo;
+  return (int)kind + 4 * gmx_bank_kernel_build(t.l0, t.l1, t.n_skip, t.has_final, t.mx[t.l0 - 1].stride);
 }
 
 // Stock kernels: only the masked (exec-per-step) forward chains, which are otherwise the

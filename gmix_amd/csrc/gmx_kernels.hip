@@ -557,16 +557,25 @@ typedef void (*gmx_bank_fn)(const GmxTopoDev*, const GmxRunArgs);
 // predictor.cpp:251-358) get the fully unrolled build, everything else the run-time one.
 // stride0 = stored length (floats) of the longest layer-0 row: <= 128 -> two rows per update
 // pass (the stock 90-input bank), 257..512 -> one row in two 256-float chunks (256 inputs).
+// Returns 1 for the two-rows-per-pass build, 2 for the two-chunk build, 0 for the run-time one
+// (gmx_debug_kernel_kind reports it to the tests).
+extern "C" int gmx_bank_kernel_build(int l0, int l1, int ns, int fin, unsigned stride0) {
+  if (l0 == 24 && l1 == 8 && ns == 1 && fin == 1) {
+    if (stride0 > 64 && stride0 <= 128) return 1;
+    if (stride0 > 256 && stride0 <= 512) return 2;
+  }
+  return 0;
+}
+
 static gmx_bank_fn gmx_pick_bank_kernel(int l0, int l1, int ns, int fin, unsigned stride0,
                                         int has_mask) {
-  if (l0 == 24 && l1 == 8 && ns == 1 && fin == 1) {
-    if (stride0 > 64 && stride0 <= 128)
-      return has_mask ? gmx_bank_kernel<true, 24, 8, 1, 1, 32, 1> : gmx_bank_kernel<false, 24, 8, 1, 1, 32, 1>;
-    if (stride0 > 256 && stride0 <= 512)
-      return has_mask ? gmx_bank_kernel<true, 24, 8, 1, 1, 64, 2> : gmx_bank_kernel<false, 24, 8, 1, 1, 64, 2>;
+  switch (gmx_bank_kernel_build(l0, l1, ns, fin, stride0)) {
+    case 1: return has_mask ? gmx_bank_kernel<true, 24, 8, 1, 1, 32, 1> : gmx_bank_kernel<false, 24, 8, 1, 1, 32, 1>;
+    case 2: return has_mask ? gmx_bank_kernel<true, 24, 8, 1, 1, 64, 2> : gmx_bank_kernel<false, 24, 8, 1, 1, 64, 2>;
+    default:
+      return has_mask ? gmx_bank_kernel<true, -1, -1, -1, -1, -1, -1>
+                      : gmx_bank_kernel<false, -1, -1, -1, -1, -1, -1>;
   }
-  return has_mask ? gmx_bank_kernel<true, -1, -1, -1, -1, -1, -1>
-                  : gmx_bank_kernel<false, -1, -1, -1, -1, -1, -1>;
 }
 
 extern "C" hipError_t gmx_launch_bank_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* args,

@@ -8,6 +8,17 @@ def _t(kind, *a, **k):
     return getattr(topology, kind)(*a, **k)
 
 
+def _24_8_1(n, tables, skip):
+    """24/8/1 with the given 33 gate-table sizes and learning rates of its own (1.3e-5 .. 0.047)."""
+    lrs = [float(f"{0.000013 * 1.31 ** ((7 * j) % 31):.3g}") for j in range(33)]
+    return topology.Topology(n, [(0 if j < 24 else 1 if j < 32 else 2, t, lr)
+                                 for j, (t, lr) in enumerate(zip(tables, lrs))], skip=(skip,))
+
+
+# gate tables that are not powers of two (a row index of ctx % t), beside some that are
+_ODD_TABLES = [3, 1000, 4097, 65537, 5, 1, 7, 1000, 3, 4097, 256, 1000, 5, 7, 3, 1, 65537, 1000, 5, 3, 7, 1000, 3, 1,
+               3, 1, 1000, 7, 256, 5, 3, 1, 3]
+
 # name -> (topology factory, T bits, bits fully dumped, synthetic-stream kwargs)
 CASES = {
     # SURVEY.md Appendix A.3 runs (hash-only, long):
@@ -29,6 +40,14 @@ CASES = {
                        dict(ctx_mode=1, ctx_mod=11, zero_mod=3, bit_mode=1)),
     "no_final_no_skip": (lambda: topology.Topology(33, [(0, 64, .01)] * 5 + [(1, 8, .01)] * 2, skip=()),
                          2000, 2000, dict(ctx_mode=1, ctx_mod=70, bit_mode=1)),
+    # the stock, unrolled-bank and wide routes (gmx_capi.cpp kernel_for) at tables that are not powers of two,
+    # contexts above every table, the skip input off index 1:
+    "stock90_odd_tables_skip45": (lambda: _24_8_1(90, _ODD_TABLES, 45), 1500, 1000,
+                                  dict(ctx_mode=1, ctx_mod=200003, zero_mod=7, bit_mode=1, seed=31)),
+    "bank24_n100_skip99": (lambda: _24_8_1(100, _ODD_TABLES[::-1], 99), 1200, 1000,
+                           dict(ctx_mode=3, ctx_mod=70001, zero_mod=5, bit_mode=1, seed=32)),
+    "wide256_odd_tables_skip0": (lambda: _24_8_1(256, _ODD_TABLES, 0), 1000, 800,
+                                 dict(ctx_mode=4, zero_mod=11, bit_mode=1, seed=33)),
     # generation mode: Learn stops at bit 800 (runner-utils.cpp:199-209)
     "stock90_nolearn_tail": (lambda: _t("stock", 90), 1200, 1200,
                              dict(ctx_mode=3, ctx_mod=9, bit_mode=1, nolearn_from=800)),

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import goldenlib
+import kernel_shapes as ks
 from gmix_amd import topology
 
 pytestmark = pytest.mark.gpu
@@ -175,17 +176,21 @@ def test_one_model_family_on_the_device(gpu, oracle, family, device_fetch, monke
             x.close()
 
 
-@pytest.mark.parametrize("kind", ["stock", "synth3", "stock_device_fetch"])
+@pytest.mark.parametrize("kind", ["stock", "synth3", "stock_device_fetch", "stock_odd"])
 def test_mixers_alone_in_lock_step(gpu, oracle, kind, monkeypatch):
     """gmx_chainstep without Indirect models and LSTM: the caller's records carry all inputs (the mixers-only drop-in).
     The reference's shape through gmx_stock_step_kernel (its inputs stored by the host, or fetched by the upload launch),
-    the 256-input 24/8/1 bank through a learn and a forward launch of the general kernel."""
+    the 256-input 24/8/1 bank through a learn and a forward launch of the general kernel.  "stock_odd": the stock
+    shape with tables that are not powers of two, the skip input at 45 and learning rates of its own."""
     if kind == "stock_device_fetch":
         monkeypatch.setenv("GMX_CS_NO_BAR", "1")
         kind = "stock"
-    topo = topology.stock(90) if kind == "stock" else topology.synth3(256, table0=1 << 8)
+    topo = {"stock": lambda: topology.stock(90), "stock_odd": lambda: ks.stock_like(2),
+            "synth3": lambda: topology.synth3(256, table0=1 << 8)}[kind]()
     N, M, S, T = topo.n_inputs, topo.n_mixers, 4, 300
     mg = gpu.MixerGroup(topo, S)
+    if kind != "synth3":  # the stock step kernel takes the shape kernel_for() sends to the stock kernel
+        assert ks.kernel_kind(mg) == ks.STOCK
     cs = gpu.ChainStep(mg)
     recs = [oracle.synth(N, M, T, seed=9 + s, ctx_mode=3, ctx_mod=5, zero_mod=4, bit_mode=1) for s in range(S)]
     refs = []

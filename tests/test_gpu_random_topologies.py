@@ -5,7 +5,7 @@ oracle, bit for bit, including the checkpoint bytes."""
 import numpy as np
 import pytest
 
-from gmix_amd import topology
+from kernel_shapes import random_case
 
 pytestmark = pytest.mark.gpu
 
@@ -14,30 +14,9 @@ def u32(x):
     return np.ascontiguousarray(x, np.float32).view(np.uint32)
 
 
-def random_topology(rng):
-    n = int(rng.choice([1, 2, 3, 7, 31, 64, 90, 129, 200, 256]))
-    l0 = int(rng.integers(1, 7))
-    l1 = int(rng.integers(0, 4))
-    fin = bool(rng.integers(0, 2)) if l1 else bool(rng.integers(0, 2))
-    n_skip = int(rng.integers(0, min(n, 3) + 1)) if (l1 or fin) else 0
-    skip = sorted(rng.choice(n, size=n_skip, replace=False).tolist()) if n_skip else []
-    sizes = [1, 2, 3, 5, 8, 100, 257, 1000, 4096]
-    mixers = [(0, int(rng.choice(sizes)), float(rng.choice([0.0005, 0.003, 0.02]))) for _ in range(l0)]
-    mixers += [(1, int(rng.choice(sizes)), float(rng.choice([0.0005, 0.003]))) for _ in range(l1)]
-    if fin:
-        mixers += [(2, int(rng.choice([1, 3, 64])), 0.001)]
-    return topology.Topology(n, mixers, skip=skip)
-
-
 @pytest.mark.parametrize("seed", range(16))
 def test_random_topology_equals_oracle(gpu, oracle, seed):
-    rng = np.random.default_rng(1000 + seed)
-    topo = random_topology(rng)
-    T = int(rng.integers(300, 900))
-    kw = dict(ctx_mode=int(rng.integers(0, 4)), ctx_mod=int(rng.choice([1, 2, 7, 300])),
-              zero_mod=int(rng.choice([0, 0, 3, 9])), bit_mode=int(rng.integers(0, 2)))
-    if seed >= 12:
-        kw["ctx_mode"] = 4 + (seed & 1)   # byte-held contexts with a few that move every bit
+    topo, T, kw, rng = random_case(seed)   # (tests/test_oracle_reference_shapes.py pins these to the reference)
     S = 3
     streams = [oracle.synth(topo.n_inputs, topo.n_mixers, T, seed=seed * 10 + s + 1, **kw) for s in range(S)]
     g = gpu.MixerGroup(topo, S)

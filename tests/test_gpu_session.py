@@ -8,6 +8,7 @@ import time
 import numpy as np
 import pytest
 
+import kernel_shapes as ks
 from gmix_amd import topology
 
 pytestmark = pytest.mark.gpu
@@ -15,6 +16,11 @@ pytestmark = pytest.mark.gpu
 
 def u32(x):
     return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def stock_topology(topo_id):
+    """The reference's own tables, or the stock shape with non-power-of-two tables and the skip input moved."""
+    return topology.stock(90) if topo_id == "stock" else ks.stock_like(2)
 
 
 def dbg(g):
@@ -39,16 +45,20 @@ def per_bit(g, rec, t0, t1, stream=0, hook=None):
     return P, O
 
 
-@pytest.mark.parametrize("sessions", ["device", "host", False])
-def test_per_bit_equals_oracle_with_interruptions(gpu, oracle, sessions):
+@pytest.mark.parametrize("sessions,topo_id", [(m, t) for t in ("stock", "stock_odd") for m in ("device", "host", False)],
+                         ids=[str(m) + ("" if t == "stock" else "-" + t)
+                              for t in ("stock", "stock_odd") for m in ("device", "host", False)])
+def test_per_bit_equals_oracle_with_interruptions(gpu, oracle, sessions, topo_id):
     """sessions: where the session's command block lives (device memory written through the BAR /
-    pinned host memory), or False for two kernel launches per bit."""
-    topo = topology.stock(90)
+    pinned host memory), or False for two kernel launches per bit.  topo_id "stock_odd": the stock shape with
+    tables that are not powers of two, the skip input at 45 and learning rates of its own (kernel_shapes)."""
+    topo = stock_topology(topo_id)
     T = 1500
     rec = oracle.synth(90, 33, T, seed=4242, ctx_mode=3, ctx_mod=5, zero_mod=7, bit_mode=1)
     ob = oracle.Bank(90, topo.skip, topo.mixers)
     p_ref, o_ref = ob.run(*rec)
     g = gpu.MixerGroup(topo, 2)
+    assert ks.kernel_kind(g) == ks.STOCK  # the shape of the stock session kernel (group_is_stock)
     L = dbg(g)
     assert L.gmx_debug_use_sessions(g.h, 1 if sessions else 0) == 0
     assert L.gmx_debug_mailbox_on_device(g.h, 0 if sessions == "host" else 1, 0, None) == 0
@@ -199,7 +209,7 @@ def test_per_bit_latency_report(gpu, capsys):
     # (figures are reported, not asserted: a loaded node or a busy PCIe link must not turn the parity gate red)
 
 
-@pytest.mark.parametrize("shape", ["stock", "general", "stock_persistent"])
+@pytest.mark.parametrize("shape", ["stock", "general", "stock_persistent", "stock_odd", "stock_odd_persistent"])
 def test_lockstep_graphs_equal_oracle(gpu, oracle, shape):
     """gmx_lockstep: every stream one bit per step, each half step one hipGraph -- or, GMX_LOCKSTEP_PERSISTENT,
     persistent waves behind one doorbell that read the records from the host arrays themselves -- the floats
@@ -207,8 +217,8 @@ def test_lockstep_graphs_equal_oracle(gpu, oracle, shape):
     at the end, two streams that stand at different bit counts; the persistent waves also across idle exits
     (before a Predict, and between a Predict and its Learn: the forward is redone from the wave's own copy)."""
     import time
-    persistent = shape.startswith("stock_persistent")
-    topo = topology.stock(90) if shape != "general" else topology.Topology(
+    persistent = shape.endswith("persistent")
+    topo = stock_topology(shape.replace("_persistent", "")) if shape != "general" else topology.Topology(
         40, [(0, 64, 0.004)] * 5 + [(1, 16, 0.003)] * 3 + [(2, 1, 0.0005)], skip=(1,))
     n, m = topo.n_inputs, topo.n_mixers
     S, T = 5, 420
@@ -218,6 +228,7 @@ def test_lockstep_graphs_equal_oracle(gpu, oracle, shape):
         ob = oracle.Bank(n, topo.skip, topo.mixers)
         refs.append((ob,) + ob.run(*recs[s], nolearn_from=400))
     g = gpu.MixerGroup(topo, S)
+    assert ks.kernel_kind(g) == (ks.BANK if shape == "general" else ks.STOCK)
     # stream 3 starts older than the others: its decay factors differ from the first step on
     pre = oracle.synth(n, m, 57, seed=5, ctx_mode=3, ctx_mod=5, bit_mode=1)
     ob3 = oracle.Bank(n, topo.skip, topo.mixers)
