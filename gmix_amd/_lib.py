@@ -87,6 +87,8 @@ def lib():
     L.gmx_batch_fill_synthetic.argtypes = [vp, u64, u64, u64, i32, u32, u32, i32]
     L.gmx_group_run.argtypes = [vp, vp, u64, i32, C.POINTER(C.c_float)]
     L.gmx_group_run_ragged.argtypes = [vp, vp, C.POINTER(u64), i32]
+    L.gmx_topology_register_rows_eligible.argtypes = [C.POINTER(TopologyStruct)]
+    L.gmx_group_set_register_rows.argtypes = [vp, i32]
     L.gmx_bank_export.argtypes = [vp, i32, vp, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_size_t)]
     L.gmx_bank_import.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.gmx_bank_copy.argtypes = [vp, i32, vp, i32]
@@ -195,7 +197,8 @@ ABI_SYMBOLS = [
     "gmx_batch_create", "gmx_batch_destroy", "gmx_batch_n_pad", "gmx_batch_mask_words",
     "gmx_batch_max_bits", "gmx_batch_predictions", "gmx_batch_active_mask", "gmx_batch_contexts",
     "gmx_batch_bits", "gmx_batch_p", "gmx_batch_outputs", "gmx_batch_last_outputs", "gmx_batch_upload", "gmx_batch_download",
-    "gmx_batch_wait", "gmx_batch_fill_synthetic", "gmx_group_run", "gmx_group_run_ragged", "gmx_bank_export",
+    "gmx_batch_wait", "gmx_batch_fill_synthetic", "gmx_group_run", "gmx_group_run_ragged",
+    "gmx_topology_register_rows_eligible", "gmx_group_set_register_rows", "gmx_bank_export",
     "gmx_bank_import", "gmx_bank_copy", "gmx_bank_memory_usage",
     "gmx_lockstep_create", "gmx_lockstep_destroy", "gmx_lockstep_batch", "gmx_lockstep_is_persistent", "gmx_lockstep_predict", "gmx_lockstep_learn", "gmx_lockstep_learn_predict",
     "gmx_indirect_create", "gmx_indirect_destroy", "gmx_indirect_n_streams", "gmx_indirect_n_models",

@@ -54,6 +54,16 @@ class Topology:
         return TopologyStruct(self.n_inputs, len(self.skip), self._skip, len(self.mixers), self._descs)
 
 
+def register_rows_eligible(topo):
+    """Whether MixerGroup.set_register_rows would accept a group of this topology (host code only):
+    three layers of 1..24 / 1..8 / 1 mixers, one skip input, 4..256 inputs."""
+    st = topo._struct()
+    rc = _lib.lib().gmx_topology_register_rows_eligible(C.byref(st))
+    if rc < 0:
+        raise GmxError(rc, "gmx_topology_register_rows_eligible")
+    return bool(rc)
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -75,6 +85,11 @@ class MixerGroup:
         w = list(words) if words else []
         arr = (C.c_uint32 * max(1, len(w)))(*w)
         check(self.L.gmx_group_set_cu_mask(self.h, arr, len(w)), "gmx_group_set_cu_mask")
+
+    def set_register_rows(self, on=True):
+        """Batched runs through the register-resident kernel for any three-layer bank (off by default; GmxError
+        for a topology register_rows_eligible() refuses).  May be flipped between launches."""
+        check(self.L.gmx_group_set_register_rows(self.h, 1 if on else 0), "gmx_group_set_register_rows")
 
     def close(self):
         if getattr(self, "h", None):

@@ -48,6 +48,9 @@ hipError_t gmx_launch_single_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* 
                                     int variant, hipStream_t stream);
 hipError_t gmx_launch_wide_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* args, int n_streams, int has_mask,
                                   int n_inputs, hipStream_t stream);
+hipError_t gmx_launch_pair_kernel(const GmxTopoDev* tp_dev, const GmxRunArgs* args, int n_streams, int has_mask,
+                                  int n_inputs, int l0, int l1, hipStream_t stream);
+int gmx_pair_kernel_half(int n_inputs);
 hipError_t gmx_launch_synth_kernel(const GmxSynthArgs* args, hipStream_t stream);
 struct GmxDecayArgs {
   const uint64_t* steps0;
@@ -338,6 +341,7 @@ struct gmx_group {
   int stock_staged = -1;           // stock kernel: rows through the LDS images (1), lane-private (0), by stream count (-1)
   bool decay_on_host = false;      // tests: the decay tables always from the host's libm loop
   bool stock_pairs = false;        // batched runs of the stock shape through gmx_wide_kernel<90, 64> (lane pairs)
+  bool register_rows = false;      // gmx_group_set_register_rows: batched runs through gmx_pair_kernel (gmx_pair.hip)
   int single_variant = 0;          // tests/tuning: lanes per stream of the single-mixer kernel (0 = default)
 };
 
@@ -877,9 +881,20 @@ static int prepare_decay(gmx_group* g, int s0, int ns, uint64_t T, int learn, gm
   return GMX_OK;
 }
 
+// The topologies gmx_pair_kernel serves (gmx_pair.hip): three layers of 1..24 / 1..8 / 1 mixers, one skip input,
+// 4..256 inputs; any tables, any rates.
+static bool topo_register_rows_eligible(const GmxTopoDev& t) {
+  return t.has_final && t.l0 >= 1 && t.l0 <= 24 && t.l1 >= 1 && t.l1 <= 8 && t.m == t.l0 + t.l1 + 1 &&
+         t.n_skip == 1 && gmx_pair_kernel_half(t.n) != 0;
+}
+
 // Which kernel a launch takes.
-enum GmxKernelKind : int { GMX_K_SINGLE, GMX_K_WIDE, GMX_K_STOCK, GMX_K_BANK };
+enum GmxKernelKind : int { GMX_K_SINGLE, GMX_K_WIDE, GMX_K_STOCK, GMX_K_BANK, GMX_K_PAIR };
 static GmxKernelKind kernel_for(const gmx_group* g, unsigned mode) {
+  // The opt-in register-resident kernel for any three-layer bank (gmx_pair.hip); batched Predict(+Learn) only.
+  if (g->register_rows && (mode & GMX_MODE_PREDICT) && !(mode & GMX_MODE_LATCH) && !g->force_general &&
+      topo_register_rows_eligible(g->topo))
+    return GMX_K_PAIR;
   // Banks that are a single layer-0 mixer take the register-resident throughput kernel
   // (gmx_single.hip); everything else, and every per-bit call, the general kernel.
   const bool single = g->topo.m == 1 && g->topo.n <= 256 && (mode & GMX_MODE_PREDICT) &&
@@ -937,7 +952,9 @@ static int launch_run(gmx_group* g, gmx_batch* b, int s0, int rec0, int ns, uint
   const GmxKernelKind kind = kernel_for(g, mode);
   const bool single = kind == GMX_K_SINGLE, wide = kind == GMX_K_WIDE, stock = kind == GMX_K_STOCK;
   if (a.out_last && (single || wide)) return GMX_ERR_INVALID;  // (gmx_batch_create refuses the flag for these shapes)
-  if (single)
+  if (kind == GMX_K_PAIR)
+    HIPCHK(gmx_launch_pair_kernel(g->topo_dev, &a, ns, a.mask != nullptr, g->topo.n, g->topo.l0, g->topo.l1, g->stream));
+  else if (single)
     HIPCHK(gmx_launch_single_kernel(g->topo_dev, &a, g->topo.n, g->single_variant, g->stream));
   else if (wide)
     HIPCHK(gmx_launch_wide_kernel(g->topo_dev, &a, ns, a.mask != nullptr, g->topo.n, g->stream));
@@ -1039,7 +1056,9 @@ extern "C" int gmx_batch_create(gmx_batch** out, gmx_group* g, uint64_t max_bits
   if (!g) return GMX_ERR_INVALID;
   if (flags & GMX_BATCH_LAST_OUTPUTS) {  // the one-mixer and lane-pair kernels do not keep them
     const GmxKernelKind kind = kernel_for(g, GMX_MODE_PREDICT | GMX_MODE_LEARN);
-    if (kind == GMX_K_SINGLE || kind == GMX_K_WIDE) return GMX_ERR_INVALID;
+    // (a group gmx_group_set_register_rows accepts may get the flag before or after the switch: its kernel keeps
+    // them; a run with the switch off that ends in one of the two kernels above is refused at the launch)
+    if ((kind == GMX_K_SINGLE || kind == GMX_K_WIDE) && !topo_register_rows_eligible(g->topo)) return GMX_ERR_INVALID;
   }
   int rc = batch_alloc(out, g, g->S, max_bits, flags);
   if (rc) return rc;
@@ -1232,7 +1251,7 @@ extern "C" int gmx_group_run_ragged(gmx_group* g, gmx_batch* b, const uint64_t* 
   // other, each at a whole kernel's latency).  The one-mixer and lane-pair kernels run the runs.
   const GmxKernelKind kind = kernel_for(g, mode);
   static const bool split = getenv("GMX_RAGGED_SPLIT") != nullptr;  // debugging: a launch per run of equal neighbours
-  if (!split && (kind == GMX_K_STOCK || kind == GMX_K_BANK)) return launch_run(g, b, 0, 0, g->S, maxn, mode, nullptr, n_bits);
+  if (!split && (kind == GMX_K_STOCK || kind == GMX_K_BANK || kind == GMX_K_PAIR)) return launch_run(g, b, 0, 0, g->S, maxn, mode, nullptr, n_bits);
   for (int s0 = 0; s0 < g->S;) {
     int s1 = s0 + 1;
     while (s1 < g->S && n_bits[s1] == n_bits[s0]) ++s1;
@@ -1547,6 +1566,19 @@ extern "C" int gmx_debug_decay_table(gmx_group* g, const uint64_t* steps0, int U
   return rc;
 }
 
+// ---- the register-resident kernel for any three-layer bank (gmx_pair.hip), opt-in -----------------------
+extern "C" int gmx_topology_register_rows_eligible(const gmx_topology* topo) {
+  GmxTopoDev td;
+  if (build_topology(topo, &td) != GMX_OK) return GMX_ERR_INVALID;
+  return topo_register_rows_eligible(td) ? 1 : 0;
+}
+
+extern "C" int gmx_group_set_register_rows(gmx_group* g, int on) {
+  if (!g || !topo_register_rows_eligible(g->topo)) return GMX_ERR_INVALID;
+  g->register_rows = on != 0;
+  return GMX_OK;
+}
+
 extern "C" int gmx_debug_force_general(gmx_group* g, int on) {
   if (!g) return GMX_ERR_INVALID;
   g->force_general = on != 0;
@@ -1554,7 +1586,7 @@ extern "C" int gmx_debug_force_general(gmx_group* g, int on) {
 }
 
 // The kernel a batched launch of `mode` (GMX_MODE_* bits) takes: kernel_for()'s kind (0 single, 1 wide, 2 stock,
-// 3 bank) plus, for the bank kernel, 4 x the build gmx_pick_bank_kernel takes (0 run-time, 1 unrolled 24/8/1 with
+// 3 bank, 4 lane pairs for any three-layer bank) plus, for the bank kernel, 4 x the build gmx_pick_bank_kernel takes (0 run-time, 1 unrolled 24/8/1 with
 // stride0 65..128, 2 unrolled 24/8/1 with stride0 257..512).  Tests assert their route with it.
 extern "C" int gmx_debug_kernel_kind(gmx_group* g, unsigned mode) {
   if (!g) return GMX_ERR_INVALID;

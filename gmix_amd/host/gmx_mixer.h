@@ -139,6 +139,10 @@ class MixerBank {
     return status_;
   }
   bool ready() const { return group_ != nullptr; }
+  // A Predictor whose AddMixers is not the stock one (another input count, other layer widths): batched runs on this
+  // bank's group through the register-resident kernel for any three-layer bank.  After Finalize; GMX_ERR_INVALID when
+  // the topology is outside that family (gmx_topology_register_rows_eligible) -- the general kernel then stays.
+  int SetRegisterRows(bool on) { return group_ ? gmx_group_set_register_rows(group_, on ? 1 : 0) : GMX_ERR_STATE; }
   // What Predictor::Predict returns for the forward pass just made (predictor.cpp:369-375).
   float last_probability() const { return last_p_; }
   int status() const { return status_; }

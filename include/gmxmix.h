@@ -121,7 +121,8 @@ int gmx_bank_learn(gmx_group* g, int stream, int bit);
                                     * blackboard (mixer_layer0_outputs, ..., final_mixer_output) holds afterwards; a
                                     * compressor needs no more, and the throughput build of the kernel then stores
                                     * nothing else beside the probabilities.  GMX_ERR_INVALID for the shapes that run
-                                    * through the one-mixer and lane-pair kernels (use GMX_BATCH_OUTPUTS there). */
+                                    * through the one-mixer and lane-pair kernels (use GMX_BATCH_OUTPUTS there), unless
+                                    * gmx_group_set_register_rows would accept the group: its kernel keeps them. */
 int gmx_batch_create(gmx_batch** out, gmx_group* g, uint64_t max_bits, unsigned flags);
 void gmx_batch_destroy(gmx_batch* b);
 /* Layout of the staging arrays (all stream-major, then bit):
@@ -180,6 +181,23 @@ int gmx_group_run(gmx_group* g, gmx_batch* b, uint64_t n_bits, int learn, float*
  * (GMX_RAGGED_SPLIT=1 in the environment forces that for every shape: a debugging aid).  The decay tables of the launch
  * are staged at a pitch of max(n_bits) for every stream.  Asynchronous on the group's stream. */
 int gmx_group_run_ragged(gmx_group* g, gmx_batch* b, const uint64_t* n_bits /* [S] */, int learn);
+
+/* ---- register-resident rows for any three-layer bank (opt-in) ---------------------------- */
+/* By default only three literal shapes run with their rows in registers (one mixer; 90 or 256 inputs x 24/8/1);
+ * every other topology takes the general kernel, which stages rows in LDS.  A bank whose AddMixers is not the
+ * reference's can ask for the lane-pair kernel that serves the whole family: exactly three layers of 1..24 layer-0
+ * mixers, 1..8 layer-1 mixers and a final mixer, exactly one skip input (at any index), 4..256 inputs, any table
+ * sizes and learning rates.
+ * gmx_topology_register_rows_eligible: 1 / 0 (host code only, no device needed); GMX_ERR_INVALID for a topology
+ * gmx_group_create refuses.
+ * gmx_group_set_register_rows: on != 0 sends gmx_group_run / gmx_group_run_ragged of this group (Predict, with or
+ * without Learn; the 90- and 256-input shapes included) through that kernel, 0 back to the default routes; off when
+ * a group is created.  GMX_ERR_INVALID, and nothing changes, when the topology is not eligible.  May be flipped
+ * between launches: a bank's state in device memory is complete after every launch and its layout is the same for
+ * every kernel.  Per-bit calls, lock step and chain steps are not affected.  Batches of such a group may be created
+ * with GMX_BATCH_LAST_OUTPUTS whatever the switch says at that moment; ragged runs are ONE launch. */
+int gmx_topology_register_rows_eligible(const gmx_topology* topo);
+int gmx_group_set_register_rows(gmx_group* g, int on);
 
 /* ---- persistence ------------------------------------------ */
 /* Byte-compatible with the reference: *short_bytes = Mixer::WriteToDisk of every mixer in
