@@ -92,6 +92,8 @@ def lib():
     L.gmx_bank_export.argtypes = [vp, i32, vp, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_size_t)]
     L.gmx_bank_import.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.gmx_bank_copy.argtypes = [vp, i32, vp, i32]
+    L.gmx_group_export.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+    L.gmx_group_import.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_size_t), vp]
     L.gmx_bank_memory_usage.argtypes = [vp, i32, i32, C.POINTER(u64)]
     L.gmx_indirect_create.argtypes = [C.POINTER(vp), C.POINTER(IndirectDesc), i32, vp, vp, i32, i32]
     L.gmx_indirect_destroy.argtypes = [vp]
@@ -199,7 +201,7 @@ ABI_SYMBOLS = [
     "gmx_batch_bits", "gmx_batch_p", "gmx_batch_outputs", "gmx_batch_last_outputs", "gmx_batch_upload", "gmx_batch_download",
     "gmx_batch_wait", "gmx_batch_fill_synthetic", "gmx_group_run", "gmx_group_run_ragged",
     "gmx_topology_register_rows_eligible", "gmx_group_set_register_rows", "gmx_bank_export",
-    "gmx_bank_import", "gmx_bank_copy", "gmx_bank_memory_usage",
+    "gmx_bank_import", "gmx_bank_copy", "gmx_group_export", "gmx_group_import", "gmx_bank_memory_usage",
     "gmx_lockstep_create", "gmx_lockstep_destroy", "gmx_lockstep_batch", "gmx_lockstep_is_persistent", "gmx_lockstep_predict", "gmx_lockstep_learn", "gmx_lockstep_learn_predict",
     "gmx_indirect_create", "gmx_indirect_destroy", "gmx_indirect_n_streams", "gmx_indirect_n_models",
     "gmx_indirect_bank_bytes", "gmx_indirect_reset", "gmx_indirect_sync", "gmx_indirect_forward", "gmx_chain_forward",

@@ -172,6 +172,34 @@ class MixerGroup:
         check(self.L.gmx_bank_import(self.h, stream, _vp(lb), len(long_bytes), _vp(sb), len(short_bytes)),
               "gmx_bank_import")
 
+    def export_all(self, first=0, count=None):
+        """[(long_bytes, short_bytes)] of streams [first, first + count) in one call (gmx_group_export): the learned
+        rows are found and packed on the device; section i is byte for byte export(first + i)."""
+        count = self.S - first if count is None else count
+        off = (C.c_size_t * (max(count, 0) + 1))()
+        check(self.L.gmx_group_export(self.h, first, count, None, 0, off, None), "gmx_group_export(size)")
+        if count == 0:
+            return []
+        ns = 24 * self.topo.n_mixers
+        lb = np.zeros(max(off[count], 1), np.uint8)
+        sb = np.zeros(count * ns, np.uint8)
+        check(self.L.gmx_group_export(self.h, first, count, _vp(lb), off[count], off, _vp(sb)), "gmx_group_export")
+        return [(lb[off[i]:off[i + 1]].tobytes(), sb[i * ns:(i + 1) * ns].tobytes()) for i in range(count)]
+
+    def import_all(self, sections, first=0):
+        """The inverse of export_all (gmx_group_import): sections[i] = (long_bytes, short_bytes) goes to stream
+        first + i.  A malformed section anywhere raises GmxError and leaves every bank as it was."""
+        count = len(sections)
+        ns = 24 * self.topo.n_mixers
+        if any(len(s) != ns for _, s in sections):
+            raise GmxError(-6, "gmx_group_import(short section)")
+        off = (C.c_size_t * (count + 1))()
+        for i, (l, _) in enumerate(sections):
+            off[i + 1] = off[i] + len(l)
+        lb = np.frombuffer(b"".join(l for l, _ in sections) or b"\0", np.uint8)
+        sb = np.frombuffer(b"".join(s for _, s in sections) or b"\0", np.uint8)
+        check(self.L.gmx_group_import(self.h, first, count, _vp(lb), off, _vp(sb)), "gmx_group_import")
+
     def copy_from(self, src, src_stream=0, dst_stream=0):
         check(self.L.gmx_bank_copy(self.h, dst_stream, src.h, src_stream), "gmx_bank_copy")
 

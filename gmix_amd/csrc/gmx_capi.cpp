@@ -21,6 +21,7 @@
 #include "../../include/gmxmix.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
+#include "gmx_ckpt.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -343,6 +344,7 @@ struct gmx_group {
   bool stock_pairs = false;        // batched runs of the stock shape through gmx_wide_kernel<90, 64> (lane pairs)
   bool register_rows = false;      // gmx_group_set_register_rows: batched runs through gmx_pair_kernel (gmx_pair.hip)
   int single_variant = 0;          // tests/tuning: lanes per stream of the single-mixer kernel (0 = default)
+  struct GmxCkptState* ckpt = nullptr;  // gmx_group_export / gmx_group_import: chunk list and staging (gmx_ckpt.inc), lazily
 };
 
 struct gmx_batch {
@@ -404,6 +406,7 @@ static GmxKernelKind kernel_for(const gmx_group* g, unsigned mode);
 static int sessions_close(gmx_group* g, bool keep_forward);
 static int locksteps_stop(gmx_group* g, gmx_lockstep* except, bool keep_forward);
 static void sessions_free(gmx_group* g);
+static void ckpt_free(gmx_group* g);
 
 extern "C" const char* gmx_strerror(int status) {
   switch (status) {
@@ -668,6 +671,7 @@ extern "C" void gmx_group_destroy(gmx_group* g) {
     if (d.ready) (void)hipEventDestroy(d.ready);
   }
   count_list_free(g->counts);
+  ckpt_free(g);
   if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
   if (g->up_stream) {
     (void)hipStreamSynchronize(g->up_stream);
@@ -1484,6 +1488,8 @@ extern "C" int gmx_bank_copy(gmx_group* dst, int dst_stream, gmx_group* src, int
   for (gmx_lockstep* ls : dst->locksteps) ls->predicted = false;
   return GMX_OK;
 }
+
+#include "gmx_ckpt.inc"
 
 extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64_t* bytes) {
   if (!g || stream < 0 || stream >= g->S || mixer < 0 || mixer >= g->topo.m || !bytes)

@@ -143,6 +143,32 @@ class MixerBank {
   // bank's group through the register-resident kernel for any three-layer bank.  After Finalize; GMX_ERR_INVALID when
   // the topology is outside that family (gmx_topology_register_rows_eligible) -- the general kernel then stays.
   int SetRegisterRows(bool on) { return group_ ? gmx_group_set_register_rows(group_, on ? 1 : 0) : GMX_ERR_STATE; }
+  // Checkpoint of every stream of this bank's group in one call (gmx_group_export / gmx_group_import): the learned
+  // rows are found and packed on the device.  Stream i's long section -- the bytes WriteToDisk writes for it -- is
+  // long_buf[long_off[i] .. long_off[i + 1]), its 3 x u64 per mixer short_buf[i * 24 * size() ..).  After Finalize.
+  // WriteToDisk / ReadFromDisk below stay on the per-stream calls (one Predictor's file at a time).
+  int ExportAll(std::vector<char>* long_buf, std::vector<size_t>* long_off, std::vector<char>* short_buf) {
+    if (!group_) return GMX_ERR_STATE;
+    const int n = gmx_group_n_streams(group_);
+    long_off->assign((size_t)n + 1, 0);
+    int rc = gmx_group_export(group_, 0, n, nullptr, 0, long_off->data(), nullptr);
+    if (rc) return rc;
+    long_buf->resize(long_off->back() ? long_off->back() : 1);
+    short_buf->resize((size_t)n * 24 * descs_.size());
+    rc = gmx_group_export(group_, 0, n, long_buf->data(), long_buf->size(), long_off->data(), short_buf->data());
+    if (rc == GMX_OK) long_buf->resize(long_off->back());
+    return rc;
+  }
+  // GMX_ERR_FORMAT, and no bank touched, when any section is malformed.
+  int ImportAll(const std::vector<char>& long_buf, const std::vector<size_t>& long_off,
+                const std::vector<char>& short_buf) {
+    if (!group_) return GMX_ERR_STATE;
+    const int n = gmx_group_n_streams(group_);
+    if (long_off.size() != (size_t)n + 1 || long_off.back() > long_buf.size() ||
+        short_buf.size() != (size_t)n * 24 * descs_.size())
+      return GMX_ERR_INVALID;
+    return gmx_group_import(group_, 0, n, long_buf.data(), long_off.data(), short_buf.data());
+  }
   // What Predictor::Predict returns for the forward pass just made (predictor.cpp:369-375).
   float last_probability() const { return last_p_; }
   int status() const { return status_; }

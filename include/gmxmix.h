@@ -209,6 +209,18 @@ int gmx_bank_import(gmx_group* g, int stream, const void* long_buf, size_t long_
                     const void* short_buf, size_t short_bytes);
 /* Predictor::Copy for the mixer slice (mixer.cpp:190-195, long-term-memory.cpp:201-214). */
 int gmx_bank_copy(gmx_group* dst, int dst_stream, gmx_group* src, int src_stream);
+/* Checkpoint streams [first, first + count) of a group in one call; the learned rows are found and packed on the
+ * device, so work and traffic follow the rows that exist, not the size of the banks.  Stream i's long section --
+ * byte for byte what gmx_bank_export gives for it -- lies at long_buf + long_off[i], long_off[i + 1] - long_off[i]
+ * bytes; its short section at short_buf + i * 24 * n_mixers.  long_off has count + 1 entries and is always filled.
+ * With long_buf == NULL and short_buf == NULL the call only sizes (long_off[count] = bytes needed).
+ * GMX_ERR_INVALID if long_cap < long_off[count]; nothing is written to long_buf then. */
+int gmx_group_export(gmx_group* g, int first, int count, void* long_buf, size_t long_cap,
+                     size_t* long_off /* [count + 1] */, void* short_buf /* [count][24 * n_mixers] */);
+/* The inverse.  Every section is validated as gmx_bank_import validates it, and the rows of a mixer must ascend
+ * strictly (GMX_ERR_FORMAT), BEFORE any bank is touched: a bad section anywhere leaves all banks as they were. */
+int gmx_group_import(gmx_group* g, int first, int count, const void* long_buf,
+                     const size_t* long_off /* [count + 1] */, const void* short_buf);
 /* Mixer::GetMemoryUsage (mixer.cpp:197-205). */
 int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64_t* bytes);
 
