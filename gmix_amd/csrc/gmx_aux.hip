@@ -174,11 +174,36 @@ extern "C" hipError_t gmx_launch_ind_synth_kernel(const GmxIndSynthArgs* args, h
 // ---------------------------------------------------------------------------------------
 // Device-side math probes for the parity tests (the same gmx_math.h the kernels use).
 // ---------------------------------------------------------------------------------------
+// what: 0 expf, 1 logistic, 2 squash-clamp; then what the LSTM byte model calls (gmx_lstm.hip): 5 logf, 6 logit,
+// 7 expm1f, 8 tanhf, 9 the logistic with the 2^(i/32) table in LDS as that kernel holds it, 10 the layer-norm
+// scale of a sum of squares, 11 Adam's step on tuples of six operands.
+__device__ __forceinline__ float gmx_math_unary(float v, int what, const uint64_t* lds_tab) {
+  switch (what) {
+    case 0: return gmx_expf(v);
+    case 1: return gmx_logistic(v);
+    case 5: return gmx_logf(v);
+    case 6: return gmx_logit(v);
+    case 7: return gmx_expm1f(v);
+    case 8: return gmx_tanhf(v);
+    case 9: return gmx_logistic_tab(v, lds_tab);
+    case 10: return gmx_lstm_norm_scale(v, (float)GMX_L_NC);
+    default: return gmx_squash_clamp(v);
+  }
+}
+
 __global__ void gmx_math_probe_kernel(const float* x, float* y, uint64_t n, int what) {
+  __shared__ uint64_t tab[32];
+  if (threadIdx.x < 32) tab[threadIdx.x] = gmx_exp2f_tab[threadIdx.x];
+  __syncthreads();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float v = x[i];
-  y[i] = what == 0 ? gmx_expf(v) : (what == 1 ? gmx_logistic(v) : gmx_squash_clamp(v));
+  if (what == 11) {
+    // x[6j .. 6j+5] = (weight, alpha, m, d1, v, d2) of tuple j, the result goes to y[6j] (the rest of y is 0)
+    const bool head = i % 6 == 0 && i + 5 < n;
+    y[i] = head ? gmx_lstm_adam_step(x[i], x[i + 1], x[i + 2], x[i + 3], x[i + 4], x[i + 5]) : 0.0f;
+    return;
+  }
+  y[i] = gmx_math_unary(x[i], what, tab);
 }
 
 // Compare device gmx_expf / gmx_logistic over a whole range of float bit patterns against a
@@ -186,6 +211,9 @@ __global__ void gmx_math_probe_kernel(const float* x, float* y, uint64_t n, int 
 // the host checksums its own: out[0] = xor-fold, out[1] = sum of the result bit patterns.
 __global__ void gmx_math_range_kernel(uint64_t lo, uint64_t count, int what,
                                       unsigned long long* out) {
+  __shared__ uint64_t tab[32];
+  if (threadIdx.x < 32) tab[threadIdx.x] = gmx_exp2f_tab[threadIdx.x];
+  __syncthreads();
   unsigned long long x = 0, sacc = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
        i += (uint64_t)gridDim.x * blockDim.x) {
@@ -223,7 +251,7 @@ __global__ void gmx_math_range_kernel(uint64_t lo, uint64_t count, int what,
       sacc += bad ? 1 : 0;
       continue;
     } else {
-      r = what == 0 ? gmx_expf(v) : (what == 1 ? gmx_logistic(v) : gmx_squash_clamp(v));
+      r = gmx_math_unary(v, what, tab);  // 0 .. 2, and 5 .. 10: the LSTM's functions
     }
     uint32_t rb = gmx_f2u(r);
     if (r != r) rb = 0x7fc00000u;  // all NaNs alike

@@ -344,7 +344,7 @@ gmx_lstm_kernel(const GmxLstmDev* __restrict__ dvp, const GmxLstmRunArgs a) {
 #pragma unroll
           for (int u = 6; u >= 0; --u) sq += nv[u] * nv[u];
         }
-        const float iv = 1.0f / sqrtf((sq / (float)NC) + 1e-5f);
+        const float iv = gmx_lstm_norm_scale(sq, (float)NC);
         L.red[wave] = iv;
         (B + dv.gate[wave].ivar)[le] = iv;
       }
@@ -615,7 +615,7 @@ gmx_lstm_kernel(const GmxLstmDev* __restrict__ dvp, const GmxLstmRunArgs a) {
       // added in the reference's order, 99 down to 0 -- and handed to Adam (lstm-layer.cpp:12-35)
       // right away; then the symbol columns and the layer-norm parameters.
       {
-        const float beta1 = 0.025f, beta2 = 0.9999f, eps = 1e-6f;
+        const float beta1 = 0.025f, beta2 = 0.9999f;
         auto adam1 = [&](float gr, float* mp, float* vp, float* wp) {
           float m = *mp * beta1;
           m += (1.0f - beta1) * gr;
@@ -623,7 +623,7 @@ gmx_lstm_kernel(const GmxLstmDev* __restrict__ dvp, const GmxLstmRunArgs a) {
           v += (1.0f - beta2) * gr * gr;
           *mp = m;
           *vp = v;
-          *wp -= alpha * ((m / d1) / (sqrtf(v / d2 + eps)));
+          *wp = gmx_lstm_adam_step(*wp, alpha, m, d1, v, d2);
         };
         const int cl = lane < NC ? lane : 0;  // idle lanes shadow cell 0 and do not store
 #pragma unroll 1
@@ -679,7 +679,7 @@ gmx_lstm_kernel(const GmxLstmDev* __restrict__ dvp, const GmxLstmRunArgs a) {
                 (B + go.update)[ix] = acc;  // NeuronLayer::update_ is part of the model's checkpoint
                 (B + go.m)[ix] = m;
                 (B + go.v)[ix] = v;
-                (B + go.weights)[ix] = aw - alpha * ((m / d1) / (sqrtf(v / d2 + eps)));
+                (B + go.weights)[ix] = gmx_lstm_adam_step(aw, alpha, m, d1, v, d2);
               }
               am = nm;
               av = nvv;
@@ -708,7 +708,7 @@ gmx_lstm_kernel(const GmxLstmDev* __restrict__ dvp, const GmxLstmRunArgs a) {
                 v += (1.0f - beta2) * ug[u] * ug[u];
                 (B + go.m)[ix] = m;
                 (B + go.v)[ix] = v;
-                (B + go.weights)[ix] = uw[u] - alpha * ((m / d1) / (sqrtf(v / d2 + eps)));
+                (B + go.weights)[ix] = gmx_lstm_adam_step(uw[u], alpha, m, d1, v, d2);
               }
             }
           }

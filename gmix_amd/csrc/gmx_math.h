@@ -363,4 +363,21 @@ GMX_HD float gmx_tanhf(float x) {
   return (jx >> 31) == 0 ? z : -z;
 }
 
+// ---- the two plain expressions of the LSTM's layers (gfx950 only) ---------------------------------
+// IEEE float divide and square root, nothing fused: their bits rest on the build flags alone
+// (-ffp-contract=off, -fno-gpu-flush-denormals-to-zero, -fhip-fp32-correctly-rounded-divide-sqrt).  gmx_lstm.hip
+// and the probes of gmx_aux.hip (gmx_debug_math_probe, what = 10, 11) call the same two functions, so what
+// tests/test_gpu_math.py compares with the host compiler's correctly rounded results is what the kernel runs.
+#if defined(__HIPCC__)
+// 1 / sqrt(mean square + 1e-5) of a gate's pre-norm sums (lstm-layer.cpp:221-241); sq = their sum of squares
+__device__ __forceinline__ float gmx_lstm_norm_scale(float sq, float cells) {
+  return 1.0f / sqrtf((sq / cells) + 1e-5f);
+}
+// the weight after Adam's step (lstm-layer.cpp:12-35): m, v the moments just updated, d1, d2 = 1 - beta^t
+__device__ __forceinline__ float gmx_lstm_adam_step(float w, float alpha, float m, float d1, float v, float d2) {
+  const float eps = 1e-6f;
+  return w - alpha * ((m / d1) / (sqrtf(v / d2 + eps)));
+}
+#endif  // __HIPCC__
+
 #endif  // GMX_MATH_H_

@@ -47,6 +47,9 @@ typedef struct gmxo_lstm {
   /* LstmModel */
   int top, mid, bot;
   float probs[NO];
+  /* not the reference's: how many elements ClipGradients has moved to +-gradient_clip so far (read-only evidence
+   * for the tests that the clip binds; part of no checkpoint) */
+  uint64_t clipped;
 } gmxo_lstm;
 
 static const float kLearningRate = 0.03f, kClip = 10.0f;
@@ -152,12 +155,18 @@ static const float* lstm_predict(gmxo_lstm* l, const float* ppm, uint32_t last_b
   return l->output[e];
 }
 
-static void clip(float* a) {
+static void clip(gmxo_lstm* l, float* a) {
   for (int i = 0; i < NC; ++i) {
-    if (a[i] < -kClip) a[i] = -kClip;
-    else if (a[i] > kClip) a[i] = kClip;
+    if (a[i] < -kClip) {
+      a[i] = -kClip;
+      ++l->clipped;
+    } else if (a[i] > kClip) {
+      a[i] = kClip;
+      ++l->clipped;
+    }
   }
 }
+uint64_t gmxo_lstm_clipped(const gmxo_lstm* l) { return l->clipped; }
 
 /* Adam (lstm-layer.cpp:12-35) on n elements */
 static void adam(float* g, float* m, float* v, float* w, int n, float t, uint64_t limit) {
@@ -242,9 +251,9 @@ static void layer_backward(gmxo_lstm* l, const float* input, int epoch, int symb
   neuron_backward(l, fg, input, epoch, symbol);
   neuron_backward(l, in, input, epoch, symbol);
   neuron_backward(l, og, input, epoch, symbol);
-  clip(l->state_error);
-  clip(l->stored_error);
-  clip(l->hidden_error);
+  clip(l, l->state_error);
+  clip(l, l->stored_error);
+  clip(l, l->hidden_error);
 }
 
 /* Lstm::Perceive (lstm.cpp:52-93) */
@@ -468,17 +477,23 @@ uint64_t gmxo_lstm_weights_hash(const gmxo_lstm* l, int with_output_layer) {
 #include "gmx_lstm_synth.h"
 
 /* The loop of oracle/ref_build/ref_lstm_harness.cpp around the restated model. */
-uint64_t gmxo_lstm_run_synth2(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uint32_t mask, uint64_t dump,
+uint64_t gmxo_lstm_run_synth3(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uint32_t mask, uint32_t family, uint64_t dump,
                               uint64_t nolearn_from, float* pred_out, uint8_t* act_out, uint32_t* ctx_out);
+uint64_t gmxo_lstm_run_synth2(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uint32_t mask, uint64_t dump,
+                              uint64_t nolearn_from, float* pred_out, uint8_t* act_out, uint32_t* ctx_out) {
+  return gmxo_lstm_run_synth3(l, n_bytes, seed, mask, 0, dump, nolearn_from, pred_out, act_out, ctx_out);
+}
 uint64_t gmxo_lstm_run_synth(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uint32_t mask, uint64_t dump,
                              float* pred_out, uint8_t* act_out, uint32_t* ctx_out) {
   return gmxo_lstm_run_synth2(l, n_bytes, seed, mask, dump, ~0ull, pred_out, act_out, ctx_out);
 }
-/* ... from byte nolearn_from on without LstmModel::Learn (the harness's --nolearn-from: generation) */
-uint64_t gmxo_lstm_run_synth2(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uint32_t mask, uint64_t dump,
+/* ... from byte nolearn_from on without LstmModel::Learn (the harness's --nolearn-from: generation); family: the
+ * input family of gmx_lstm_synth.h (the harness's --family) */
+uint64_t gmxo_lstm_run_synth3(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uint32_t mask, uint32_t family, uint64_t dump,
                               uint64_t nolearn_from, float* pred_out, uint8_t* act_out, uint32_t* ctx_out) {
   gmx_lstm_synth g;
   gmx_lstm_synth_init(&g, seed, mask);
+  g.family = family;
   float ppm[256], cur_ppm[256];
   uint64_t h = 0xcbf29ce484222325ull;
   int recent_bits = 1, new_bit = 0;
@@ -512,10 +527,15 @@ uint64_t gmxo_lstm_run_synth2(gmxo_lstm* l, uint64_t n_bytes, uint64_t seed, uin
 }
 
 /* The synthetic stream as arrays: ppm[n][256], bytes[n]. */
-void gmxo_lstm_synth_fill(uint64_t seed, uint32_t mask, uint64_t n, float* ppm, uint8_t* bytes) {
+void gmxo_lstm_synth_fill2(uint64_t seed, uint32_t mask, uint32_t family, uint64_t n, float* ppm, uint8_t* bytes) {
   gmx_lstm_synth g;
   gmx_lstm_synth_init(&g, seed, mask);
+  g.family = family;
   for (uint64_t i = 0; i < n; ++i) bytes[i] = (uint8_t)gmx_lstm_synth_byte(&g, ppm + i * 256);
+}
+
+void gmxo_lstm_synth_fill(uint64_t seed, uint32_t mask, uint64_t n, float* ppm, uint8_t* bytes) {
+  gmxo_lstm_synth_fill2(seed, mask, 0, n, ppm, bytes);
 }
 
 /* Same bookkeeping as gmxo_lstm_run_synth on caller-supplied records (what the device kernel

@@ -26,7 +26,8 @@ def lib():
     global _LIB
     if _LIB is None:
         path = os.path.join(_HERE, "libgmxoracle.so")
-        src = [os.path.join(_HERE, f) for f in ("gmx_oracle.c", "gmx_oracle_ind.c", "gmx_synth.h", "gmx_ind_synth.h")]
+        src = [os.path.join(_HERE, f) for f in ("gmx_oracle.c", "gmx_oracle_ind.c", "gmx_oracle_lstm.c", "gmx_synth.h", "gmx_ind_synth.h",
+                                                  "gmx_lstm_synth.h")]
         if not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(f) for f in src):
             subprocess.check_call(["make", "-s", "-C", _HERE, "all"])
         L = C.CDLL(path)
@@ -346,6 +347,12 @@ def _lstm_lib():
         L.gmxo_lstm_run_synth2.restype = C.c_uint64
         L.gmxo_lstm_run_synth2.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gmxo_lstm_run_synth3.restype = C.c_uint64
+        L.gmxo_lstm_run_synth3.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gmxo_lstm_synth_fill2.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gmxo_lstm_clipped.restype = C.c_uint64
+        L.gmxo_lstm_clipped.argtypes = [C.c_void_p]
         L.gmxo_srand.argtypes = [C.c_uint]
         L.gmxo_lstm_synth_fill.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gmxo_lstm_run.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32),
@@ -386,6 +393,16 @@ class LstmModel:
         w = np.zeros((3, 50, 563), np.float32)
         self.L.gmxo_lstm_get_weights(self.h, _p(w))
         return w
+
+    def set_weights(self, w):
+        """The three gates' weight matrices [3][50][563] (LongTermMemory::neuron_layer_weights) from the caller."""
+        w = np.ascontiguousarray(w, np.float32)
+        assert w.shape == (3, 50, 563)
+        self.L.gmxo_lstm_set_weights(self.h, _p(w))
+
+    def clipped(self):
+        """How many gradient elements ClipGradients has moved to +-10 so far (the oracle's own counter)."""
+        return int(self.L.gmxo_lstm_clipped(self.h))
 
     def output_layer(self):
         o = np.zeros((100, 256, 51), np.float32)
@@ -453,13 +470,13 @@ class LstmModel:
                              C.byref(self._cx), _p(pred), _p(act), _p(ctx))
         return pred, act, ctx
 
-    def run_synth(self, n_bytes, seed=0, mask=255, dump=0, nolearn_from=None):
+    def run_synth(self, n_bytes, seed=0, mask=255, dump=0, nolearn_from=None, family=0):
         """Drive the model with oracle/gmx_lstm_synth.h like the reference harness does; returns
         (fnv over all bits, predictions[dump,8], active[dump,8], context[dump])."""
         pred = np.zeros((dump, 8), np.float32)
         act = np.zeros((dump, 8), np.uint8)
         ctx = np.zeros(dump, np.uint32)
-        h = self.L.gmxo_lstm_run_synth2(self.h, n_bytes, seed, mask, dump,
+        h = self.L.gmxo_lstm_run_synth3(self.h, n_bytes, seed, mask, family, dump,
                                         (1 << 64) - 1 if nolearn_from is None else nolearn_from, _p(pred), _p(act), _p(ctx))
         return int(h), pred, act, ctx
 
@@ -490,12 +507,12 @@ def read_lstm_dump(path):
                 short_size=short_size, short_hash=hs, top=top, mid=mid, bot=bot, probs=probs)
 
 
-def lstm_synth(n_bytes, seed=0, mask=255):
-    """(ppm[n,256] f32, bytes[n] u8) of oracle/gmx_lstm_synth.h."""
+def lstm_synth(n_bytes, seed=0, mask=255, family=0):
+    """(ppm[n,256] f32, bytes[n] u8) of oracle/gmx_lstm_synth.h (family 1: one-hot, uniform and sparse ppm, runs)."""
     L = _lstm_lib()
     ppm = np.zeros((n_bytes, 256), np.float32)
     data = np.zeros(n_bytes, np.uint8)
-    L.gmxo_lstm_synth_fill(seed, mask, n_bytes, _p(ppm), _p(data))
+    L.gmxo_lstm_synth_fill2(seed, mask, family, n_bytes, _p(ppm), _p(data))
     return ppm, data
 
 

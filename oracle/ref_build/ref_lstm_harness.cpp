@@ -6,7 +6,10 @@
 // last_byte), ModPPMD's ppm_predictions refreshed at byte boundaries, LstmModel::Predict, new_bit,
 // LstmModel::Learn.  Input: oracle/gmx_lstm_synth.h.  Ground truth for oracle/gmx_oracle_lstm.c.
 //
-// usage: ref_lstm_harness --bytes N [--dump D] [--seed S] [--mask M] [--nolearn-from N0] --out file
+// usage: ref_lstm_harness --bytes N [--dump D] [--seed S] [--mask M] [--family F] [--state PREFIX] [--nolearn-from N0] --out file
+//   --family F: the input family of gmx_lstm_synth.h (1: one-hot, uniform and sparse ppm, runs of identical bytes)
+//   --state PREFIX: after construction the model starts from PREFIX.long (LongTermMemory::ReadFromDisk) and
+//   PREFIX.short (LstmModel::ReadFromDisk), files in the format the reference's own WriteToDisk gives them
 //   --nolearn-from N0: from byte N0 on LstmModel::Learn is not called (generation, runner-utils.cpp:199-209: Predict and
 //   Perceive only) -- Lstm::Predict then runs on output layers and histories no Perceive has refreshed
 // dump format "GMXL": u32 magic, N, D; u64 fnv of the initial gate weights;
@@ -39,8 +42,8 @@ static uint64_t Fnv(uint64_t h, const void* p, size_t n) {
 
 int main(int argc, char** argv) {
   uint64_t N = 300, dump = 0, seed = 0, nolearn_from = ~0ull;
-  uint32_t mask = 255;
-  std::string out_path;
+  uint32_t mask = 255, family = 0;
+  std::string out_path, state;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -48,6 +51,8 @@ int main(int argc, char** argv) {
     else if (a == "--dump") dump = strtoull(next().c_str(), 0, 0);
     else if (a == "--seed") seed = strtoull(next().c_str(), 0, 0);
     else if (a == "--mask") mask = (uint32_t)strtoul(next().c_str(), 0, 0);
+    else if (a == "--family") family = (uint32_t)strtoul(next().c_str(), 0, 0);
+    else if (a == "--state") state = next();
     else if (a == "--nolearn-from") nolearn_from = strtoull(next().c_str(), 0, 0);
     else if (a == "--out") out_path = next();
     else { fprintf(stderr, "unknown arg %s\n", a.c_str()); return 2; }
@@ -61,6 +66,12 @@ int main(int argc, char** argv) {
   LstmModel model(stm, ltm, false);
   stm.predictions.resize(stm.num_predictions);
   stm.predictions = 0;
+  if (!state.empty()) {
+    std::ifstream lf(state + ".long", std::ios::binary), sf(state + ".short", std::ios::binary);
+    if (!lf || !sf) { fprintf(stderr, "cannot read %s.long / .short\n", state.c_str()); return 2; }
+    ltm.ReadFromDisk(&lf);
+    model.ReadFromDisk(&sf);
+  }
 
   std::ofstream out(out_path, std::ios::binary);
   Put(out, (uint32_t)0x4c584d47u);  // "GMXL"
@@ -73,6 +84,7 @@ int main(int argc, char** argv) {
 
   gmx_lstm_synth g;
   gmx_lstm_synth_init(&g, seed, mask);
+  g.family = family;
   float ppm[256];
   uint64_t h = 0xcbf29ce484222325ull;
   uint32_t byte = gmx_lstm_synth_byte(&g, ppm);  // first byte to code and what PPM says about it

@@ -82,4 +82,30 @@ LSTM_CASES = {
     # layers no Perceive refreshes, across the epoch wrap at byte 300; the file at the end is the kind the
     # reference's TestGeneration writes (tester.cpp:312): the newest forward never perceived
     "lstm_generation": (360, 360, dict(seed=11, mask=63, nolearn_from=230)),
+    # The hard regimes (LSTM_REGIMES below).  `state`: the run starts from checkpoint files the reference reads with its
+    # own ReadFromDisk (tests/goldenlib.py, lstm_start_state: the 0xDEADBEEF model after `warm` learned bytes, its
+    # layer-norm gains x `gain`, its output layer x `out_scale`); `family`: the input family of gmx_lstm_synth.h.
+    # 330 bytes from epoch 30: backward passes at bytes 70, 170 and 270.
+    "lstm_saturated": (330, 300, dict(seed=41, mask=63, state=dict(warm=(130, 17, 63), gain=12.0, out_scale=300.0))),
+    # one-hot / uniform / sparse ppm and runs of identical bytes on the untouched initialisation, three backward passes
+    "lstm_onehot": (330, 300, dict(seed=43, family=1)),
+    # a model sure of itself on a stream whose true byte often has probability exactly 0: errors of +-1 through an
+    # output layer 400 times its learned size
+    "lstm_clipped": (330, 300, dict(seed=42, family=1, state=dict(warm=(130, 17, 63), gain=2.0, out_scale=400.0))),
+}
+
+# What the ORACLE says the first 200 bytes of each regime reach (tests/goldenlib.py, lstm_regime_evidence; the tests
+# recount and compare before they look at a kernel): silent bits (denom == 0, the previous prediction repeated), softmax
+# outputs exactly 0.0f, predictions at Sigmoid::Logit's clamp, gradient elements ClipGradients moved to +-10, input-node
+# pre-activations beyond +-22 (tanhf's saturated branch).  `needs`: the counts the regime exists for.  lstm_onehot's
+# evidence is its input: exact zeros, exact ones, uniform rows, repeated bytes, true bytes of probability 0.
+LSTM_REGIMES = {
+    "lstm_saturated": dict(bytes=200, needs=("silent_bits", "zero_probs", "saturated_gates", "clamped_logits"),
+                           counts=dict(silent_bits=308, zero_probs=49457, clamped_logits=1351, clipped=9068,
+                                       saturated_gates=243)),
+    "lstm_onehot": dict(bytes=200, needs=(), counts=None,
+                        input_counts=dict(zeros=57197, ones=166, uniform_rows=86, repeats=113, true_byte_zero=104)),
+    "lstm_clipped": dict(bytes=200, needs=("clipped", "zero_probs", "silent_bits"),
+                         counts=dict(silent_bits=1048, zero_probs=44835, clamped_logits=1455, clipped=7914,
+                                     saturated_gates=0)),
 }

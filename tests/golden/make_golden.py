@@ -99,7 +99,17 @@ def run_lstm_case(name):
             "--seed", str(kw.get("seed", 0)), "--mask", str(kw.get("mask", 255))]
     if "nolearn_from" in kw:
         args += ["--nolearn-from", str(kw["nolearn_from"])]
+    if "family" in kw:
+        args += ["--family", str(kw["family"])]
     with tempfile.TemporaryDirectory() as td:
+        if "state" in kw:  # the run starts from files the reference reads with its own ReadFromDisk
+            import goldenlib
+            lng, sh = goldenlib.lstm_start_state(gmxo, kw["state"])
+            with open(os.path.join(td, "start.long"), "wb") as f:
+                f.write(lng + bytes(8))  # (+ LongTermMemory's history count: none; no other section exists here)
+            with open(os.path.join(td, "start.short"), "wb") as f:
+                f.write(sh)
+            args += ["--state", os.path.join(td, "start")]
         out = os.path.join(td, "d.bin")
         subprocess.run(args + ["--out", out], check=True, stdout=subprocess.DEVNULL)
         d = gmxo.read_lstm_dump(out)
@@ -107,7 +117,8 @@ def run_lstm_case(name):
                 init_weights_hash=int(d["init_weights_hash"]), long_hash=int(d["long_hash"]),
                 usage=int(d["usage"]), short_size=int(d["short_size"]), short_hash=int(d["short_hash"]),
                 top=int(d["top"]), mid=int(d["mid"]), bot=int(d["bot"]),
-                source="oracle/_ref/ref_lstm_harness (reference LstmModel after srand(0xDEADBEEF), g++ -O2 strict)")
+                source="oracle/_ref/ref_lstm_harness (reference LstmModel after srand(0xDEADBEEF), g++ -O2 strict)"
+                       + (" started from state files through its ReadFromDisk" if "state" in kw else ""))
     np.savez_compressed(os.path.join(HERE, name + ".npz"), meta=json.dumps(meta), pred=d["pred"].view(np.uint32),
                         active=d["active"], ctx=d["ctx"], probs=d["probs"].view(np.uint32))
     print(f"{name}: bytes={n_bytes} dump={dump} h64={d['h64']:016x} long={d['long_hash']:016x}")

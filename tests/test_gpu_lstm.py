@@ -34,11 +34,12 @@ def run_gpu(gpu, g, streams, chunk, learn=True):
     return P, A, Cx
 
 
-@pytest.fixture(params=["1", "2"], ids=["one_workgroup_per_cu_build", "two_per_cu_build"])
+@pytest.fixture(params=["1", "2", "3"], ids=["one_workgroup_per_cu_build", "two_per_cu_build", "three_per_cu_build"])
 def lstm_build(request):
     """The batched LSTM kernel has a build for launches of at most one workgroup per CU (<= 256 streams: every launch
-    of these tests) and one for more streams (what bench.py's 1 024 streams run): GMX_LSTM_BUILD, read by the launcher
-    at every launch, puts each test through both."""
+    of these tests), one for more streams (what bench.py's 1 024 streams run) and a third with stretches of 77 weights
+    that only GMX_LSTM_BUILD=3 selects: GMX_LSTM_BUILD, read by the launcher at every launch, puts each test through
+    all three."""
     import os
     old = os.environ.get("GMX_LSTM_BUILD")
     os.environ["GMX_LSTM_BUILD"] = request.param

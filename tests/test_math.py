@@ -59,3 +59,14 @@ def test_lstm_math_equals_libm_everywhere(mc, fn):
     bad = np.zeros(16, np.uint32)
     n = getattr(mc, f"gmx_check_{fn}_range")(0, 0xFFFFFFFF, bad.ctypes.data, 16)
     assert n == 0, (n, [hex(b) for b in bad[:min(n, 16)]])
+
+
+@pytest.mark.slow
+def test_logit_equals_reference_everywhere(mc):
+    """gmx_logit (the LSTM's bit predictions go through it) against Sigmoid::Logit on the machine's libm -- double
+    comparisons and clamps, a float divide, logf -- for every float."""
+    mc.gmx_check_logit_range.restype = C.c_uint64
+    mc.gmx_check_logit_range.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p, C.c_int]
+    bad = np.zeros(16, np.uint32)
+    n = mc.gmx_check_logit_range(0, 0xFFFFFFFF, bad.ctypes.data, 16)
+    assert n == 0, (n, [hex(b) for b in bad[:min(n, 16)]])

@@ -7,17 +7,18 @@ import numpy as np
 import pytest
 
 import goldenlib
-from golden.cases import LSTM_CASES
+from golden.cases import LSTM_CASES, LSTM_REGIMES
 
 
 @pytest.mark.parametrize("name", sorted(LSTM_CASES))
 def test_lstm_oracle_matches_reference(oracle, name):
     meta, z = goldenlib.load(name)
-    m = oracle.LstmModel()                       # srand(0xDEADBEEF) + the constructor chain
-    assert m.weights_hash() == meta["init_weights_hash"]
     kw = meta["synth"]
+    # srand(0xDEADBEEF) + the constructor chain; the hard regimes then read a state file, as the reference did
+    m, _ = goldenlib.lstm_start_model(oracle, kw)
+    assert m.weights_hash() == meta["init_weights_hash"]
     h, pred, act, ctx = m.run_synth(meta["bytes"], seed=kw.get("seed", 0), mask=kw.get("mask", 255), dump=meta["dump"],
-                                    nolearn_from=kw.get("nolearn_from"))
+                                    nolearn_from=kw.get("nolearn_from"), family=kw.get("family", 0))
     if meta["dump"]:
         assert np.array_equal(pred.view(np.uint32), z["pred"])
         assert np.array_equal(act, z["active"]) and np.array_equal(ctx, z["ctx"])
@@ -54,3 +55,31 @@ def test_lstm_learns_the_synthetic_stream(oracle):
     late = np.abs(pred[2500:]).mean()
     early = np.abs(pred[:100]).mean()
     assert act[2500:].all() and late > 2 * early
+
+
+@pytest.mark.parametrize("name", sorted(LSTM_REGIMES))
+def test_lstm_regimes_reach_their_branches(oracle, name):
+    """The hard-regime fixtures are only worth their name if the branches they exist for run: recounted here from the
+    oracle's own outputs (and its clip counter), compared with the counts recorded beside the cases."""
+    reg = LSTM_REGIMES[name]
+    kw = LSTM_CASES[name][2]
+    ev, _ = goldenlib.lstm_regime_evidence(oracle, kw, reg["bytes"])
+    for k in reg["needs"]:
+        assert ev[k] > 0, (k, ev)
+    if reg["counts"] is not None:
+        assert ev == reg["counts"]
+    if "input_counts" in reg:
+        assert goldenlib.lstm_input_evidence(oracle, kw, LSTM_CASES[name][0]) == reg["input_counts"]
+        assert all(v > 0 for v in reg["input_counts"].values())
+
+
+def test_lstm_set_weights_round_trip(oracle):
+    """LstmModel.set_weights: a model given another's matrices has its hash and predicts like it."""
+    a, b = oracle.LstmModel(), oracle.LstmModel(srand_seed=5)
+    assert a.weights_hash() != b.weights_hash()
+    b.set_weights(a.weights())
+    assert a.weights_hash() == b.weights_hash()
+    ppm, data = oracle.lstm_synth(120, seed=2, family=1)
+    for x, y in zip(a.run(ppm, data), b.run(ppm, data)):
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
+    assert a.export_long() == b.export_long()
