@@ -22,6 +22,7 @@
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_ckpt.h"
+#include "gmx_ind_ckpt.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -1509,6 +1510,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 
 
 #include "gmx_indirect.inc"
+#include "gmx_ind_ckpt.inc"
 #include "gmx_lstm.inc"
 #include "gmx_chainstep.inc"
 

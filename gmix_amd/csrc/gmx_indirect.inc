@@ -41,7 +41,9 @@ struct gmx_indirect {
   GmxCountList counts;                          // per-stream bit counts of ragged launches
   std::vector<struct GmxIndSession*> sessions;  // per-bit sessions (gmx_indirect_session_kernel), per stream
   bool use_sessions = true;
+  struct GmxIndCkptState* ckpt = nullptr;  // gmx_indirect_group_export / _import: chunk list and staging (gmx_ind_ckpt.inc), lazily
 };
+static void ind_ckpt_free(gmx_indirect* ib);
 
 // ---- per-bit sessions: gmx_indirect_forward / gmx_indirect_learn without a kernel launch per call -----
 // The host side mirrors gmx_session.inc (same mailbox protocol, same bounded waits, the same count of open
@@ -116,6 +118,7 @@ extern "C" void gmx_indirect_destroy(gmx_indirect* ib) {
     ind_batch_free(ib->one);
     ib->one = nullptr;
   }
+  ind_ckpt_free(ib);
   for (gmx_ind_batch* b : ib->batches) b->ib = nullptr;  // shells, as for gmx_batch
   ib->batches.clear();
   if (ib->banks) (void)hipFree(ib->banks);

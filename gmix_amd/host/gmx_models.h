@@ -98,6 +98,28 @@ class IndirectBank {
     if (!h_ || !orig->h_) return;
     Note(gmx_indirect_copy(h_, 0, orig->h_, 0));
   }
+  // Checkpoint of every stream of this bank's gmx_indirect in one call (gmx_indirect_group_export /
+  // gmx_indirect_group_import): the live entries are found and packed on the device.  Stream i's section -- the bytes
+  // WriteToDisk writes for it -- is buf[off[i] .. off[i + 1]).  After Finalize.  WriteToDisk / ReadFromDisk above stay
+  // on the per-stream calls (one Predictor's file at a time).
+  int ExportAll(std::vector<char>* buf, std::vector<size_t>* off) {
+    if (!h_) return GMX_ERR_STATE;
+    const int n = gmx_indirect_n_streams(h_);
+    off->assign((size_t)n + 1, 0);
+    int rc = gmx_indirect_group_export(h_, 0, n, nullptr, 0, off->data());
+    if (rc) return rc;
+    buf->resize(off->back() ? off->back() : 1);
+    rc = gmx_indirect_group_export(h_, 0, n, buf->data(), buf->size(), off->data());
+    if (rc == GMX_OK) buf->resize(off->back());
+    return rc;
+  }
+  // GMX_ERR_FORMAT, and no bank touched, when any section is malformed.
+  int ImportAll(const std::vector<char>& buf, const std::vector<size_t>& off) {
+    if (!h_) return GMX_ERR_STATE;
+    const int n = gmx_indirect_n_streams(h_);
+    if (off.size() != (size_t)n + 1 || off.back() > buf.size()) return GMX_ERR_INVALID;
+    return gmx_indirect_group_import(h_, 0, n, buf.data(), off.data());
+  }
 
  private:
   friend class Indirect;

@@ -8,6 +8,10 @@ from . import _lib
 from ._lib import GmxError, IndirectDesc, check
 
 
+# Entries of a model's table that one block of the group checkpoint kernels walks (GMX_IND_CKPT_CHUNK, gmx_ind_ckpt.h)
+CKPT_CHUNK = 16384
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -110,6 +114,29 @@ class IndirectGroup:
     def import_(self, data, stream=0):
         b = np.frombuffer(data, np.uint8)
         check(self.L.gmx_indirect_import(self.h, stream, _vp(b), len(b)), "gmx_indirect_import")
+
+    def export_all(self, first=0, count=None):
+        """[bytes] of streams [first, first + count) in one call (gmx_indirect_group_export): the live entries are
+        found and packed on the device; section i is byte for byte export(first + i)."""
+        count = self.S - first if count is None else count
+        off = (C.c_size_t * (max(count, 0) + 1))()
+        check(self.L.gmx_indirect_group_export(self.h, first, count, None, 0, off), "gmx_indirect_group_export(size)")
+        if count == 0:
+            return []
+        buf = np.zeros(max(off[count], 1), np.uint8)
+        check(self.L.gmx_indirect_group_export(self.h, first, count, _vp(buf), off[count], off),
+              "gmx_indirect_group_export")
+        return [buf[off[i]:off[i + 1]].tobytes() for i in range(count)]
+
+    def import_all(self, sections, first=0):
+        """The inverse of export_all (gmx_indirect_group_import): sections[i] goes to stream first + i.  A malformed
+        section anywhere raises GmxError and leaves every bank as it was."""
+        count = len(sections)
+        off = (C.c_size_t * (count + 1))()
+        for i, sec in enumerate(sections):
+            off[i + 1] = off[i] + len(sec)
+        buf = np.frombuffer(b"".join(sections) or b"\0", np.uint8)
+        check(self.L.gmx_indirect_group_import(self.h, first, count, _vp(buf), off), "gmx_indirect_group_import")
 
     def copy_from(self, src, src_stream=0, dst_stream=0):
         check(self.L.gmx_indirect_copy(self.h, dst_stream, src.h, src_stream), "gmx_indirect_copy")

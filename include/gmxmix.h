@@ -348,6 +348,16 @@ int gmx_indirect_export(gmx_indirect* ib, int stream, void* buf, size_t* bytes);
 int gmx_indirect_import(gmx_indirect* ib, int stream, const void* buf, size_t bytes);
 int gmx_indirect_copy(gmx_indirect* dst, int dst_stream, gmx_indirect* src, int src_stream);
 int gmx_indirect_memory_usage(gmx_indirect* ib, int model, uint64_t* bytes);
+/* Checkpoint streams [first, first + count) of an Indirect group in one call; live entries are found and packed on
+ * the device.  Stream i's section -- byte for byte what gmx_indirect_export gives for it -- lies at
+ * buf + off[i], off[i + 1] - off[i] bytes.  off has count + 1 entries and is always filled.  buf == NULL only sizes.
+ * GMX_ERR_INVALID if cap < off[count]; nothing is written to buf then. */
+int gmx_indirect_group_export(gmx_indirect* ib, int first, int count, void* buf, size_t cap,
+                              size_t* off /* [count + 1] */);
+/* The inverse.  Every section is validated as gmx_indirect_import validates it, and the keys of a sparse model must
+ * ascend strictly (GMX_ERR_FORMAT), BEFORE any bank is touched: a bad section anywhere leaves all banks as they were. */
+int gmx_indirect_group_import(gmx_indirect* ib, int first, int count, const void* buf,
+                              const size_t* off /* [count + 1] */);
 
 /* What the two blackboard slots of each model hold ([2i] indirect, [2i+1] run map): ShortTermMemory::predictions at
  * slot_indirect / slot_run_map, which the reference writes with the blackboard (short-term-memory.cpp:4) and which a
