@@ -6,6 +6,8 @@ from ._lib import ABI_SYMBOLS, LIB_PATH, GmxError, build
 from .bank import Batch, ChainStep, Lockstep, MixerGroup, Topology, device_count
 from .indirect import IndirectBatch, IndirectGroup
 from .lstm import LstmBatch, LstmGroup
+from .match import MatchBatch, MatchGroup
 
 __all__ = ["topology", "ABI_SYMBOLS", "LIB_PATH", "GmxError", "build", "Batch", "MixerGroup",
-           "Lockstep", "ChainStep", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch"]
+           "Lockstep", "ChainStep", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch",
+           "MatchGroup", "MatchBatch"]

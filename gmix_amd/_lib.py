@@ -28,6 +28,10 @@ class IndirectDesc(C.Structure):
                 ("slot_run_map", C.c_int32)]
 
 
+class MatchDesc(C.Structure):
+    _fields_ = [("table_size", C.c_uint32), ("limit", C.c_int32), ("slot", C.c_int32)]
+
+
 class TopologyStruct(C.Structure):
     _fields_ = [("n_inputs", C.c_int32), ("n_skip", C.c_int32), ("skip_index", C.POINTER(C.c_int32)),
                 ("n_mixers", C.c_int32), ("mixers", C.POINTER(MixerDesc))]
@@ -158,6 +162,36 @@ def lib():
     L.gmx_lstm_import.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.gmx_lstm_copy.argtypes = [vp, i32, vp, i32]
     L.gmx_lstm_memory_usage.argtypes = [vp, C.POINTER(u64)]
+    L.gmx_match_create.argtypes = [C.POINTER(vp), C.POINTER(MatchDesc), i32, u64, i32, i32]
+    L.gmx_match_destroy.argtypes = [vp]
+    L.gmx_match_destroy.restype = None
+    for f in (L.gmx_match_n_streams, L.gmx_match_n_models, L.gmx_match_reset, L.gmx_match_sync):
+        f.argtypes = [vp]
+    L.gmx_match_bank_bytes.argtypes = [vp]
+    L.gmx_match_bank_bytes.restype = u64
+    L.gmx_match_batch_create.argtypes = [C.POINTER(vp), vp, u64]
+    L.gmx_match_batch_destroy.argtypes = [vp]
+    L.gmx_match_batch_destroy.restype = None
+    L.gmx_match_batch_max_bits.argtypes = [vp]
+    L.gmx_match_batch_max_bits.restype = u64
+    for name in ("contexts", "bit_contexts", "bits", "predictions", "active", "longest"):
+        f = getattr(L, "gmx_match_batch_" + name)
+        f.argtypes = [vp]
+        f.restype = vp
+    L.gmx_match_batch_upload.argtypes = [vp, u64]
+    L.gmx_match_batch_download.argtypes = [vp, u64]
+    L.gmx_match_batch_wait.argtypes = [vp]
+    L.gmx_match_run.argtypes = [vp, vp, u64, vp, C.POINTER(C.c_int32), i32, C.POINTER(C.c_float)]
+    L.gmx_match_run_ragged.argtypes = [vp, vp, C.POINTER(u64), vp, C.POINTER(C.c_int32), i32]
+    L.gmx_match_forward.argtypes = [vp, i32, vp, u32, vp, vp, C.POINTER(u32)]
+    L.gmx_match_learn.argtypes = [vp, i32, i32]
+    L.gmx_match_slots_get.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    L.gmx_match_slots_set.argtypes = [vp, i32, C.POINTER(C.c_float), i32]
+    L.gmx_match_history_size.argtypes = [vp, i32, C.POINTER(u64)]
+    L.gmx_match_export.argtypes = [vp, i32, vp, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_size_t)]
+    L.gmx_match_import.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
+    L.gmx_match_copy.argtypes = [vp, i32, vp, i32]
+    L.gmx_match_memory_usage.argtypes = [vp, i32, C.POINTER(u64)]
     L.gmx_lockstep_create.argtypes = [C.POINTER(vp), vp, C.c_uint]
     L.gmx_lockstep_destroy.argtypes = [vp]
     L.gmx_lockstep_destroy.restype = None
@@ -180,7 +214,7 @@ def lib():
         f = getattr(L, "gmx_chainstep_" + name)
         f.argtypes = [vp]
         f.restype = vp
-    for name in ("gmx_group_set_cu_mask", "gmx_indirect_set_cu_mask", "gmx_lstm_set_cu_mask"):
+    for name in ("gmx_group_set_cu_mask", "gmx_indirect_set_cu_mask", "gmx_lstm_set_cu_mask", "gmx_match_set_cu_mask"):
         getattr(L, name).argtypes = [vp, C.POINTER(u32), i32]
     L.gmx_debug_math_probe.argtypes = [i32, vp, vp, u64, i32]
     L.gmx_debug_math_range.argtypes = [i32, u64, u64, i32, C.POINTER(C.c_ulonglong)]
@@ -223,4 +257,11 @@ ABI_SYMBOLS = [
     "gmx_chainstep_ppm", "gmx_chainstep_bits", "gmx_chainstep_what", "gmx_chainstep_p", "gmx_chainstep_outputs",
     "gmx_chainstep_commit", "gmx_chainstep_step", "gmx_chainstep_launch", "gmx_chainstep_wait",
     "gmx_group_set_cu_mask", "gmx_indirect_set_cu_mask", "gmx_lstm_set_cu_mask",
+    "gmx_match_create", "gmx_match_destroy", "gmx_match_n_streams", "gmx_match_n_models", "gmx_match_bank_bytes",
+    "gmx_match_reset", "gmx_match_sync", "gmx_match_set_cu_mask", "gmx_match_batch_create", "gmx_match_batch_destroy",
+    "gmx_match_batch_max_bits", "gmx_match_batch_contexts", "gmx_match_batch_bit_contexts", "gmx_match_batch_bits",
+    "gmx_match_batch_predictions", "gmx_match_batch_active", "gmx_match_batch_longest", "gmx_match_batch_upload",
+    "gmx_match_batch_download", "gmx_match_batch_wait", "gmx_match_run", "gmx_match_run_ragged", "gmx_match_forward",
+    "gmx_match_learn", "gmx_match_slots_get", "gmx_match_slots_set", "gmx_match_history_size", "gmx_match_export",
+    "gmx_match_import", "gmx_match_copy", "gmx_match_memory_usage",
 ]

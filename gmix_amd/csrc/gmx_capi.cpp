@@ -23,6 +23,7 @@
 #include "gmx_internal.h"
 #include "gmx_ckpt.h"
 #include "gmx_ind_ckpt.h"
+#include "gmx_match.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -144,7 +145,8 @@ static int xfer_writer_done(GmxXfer& x, hipStream_t writer, hipStream_t main) {
 // kernel it has nothing to do with (measured: 6.2 us per bit for one compressor instead of 4.0; GPU_MAX_HW_QUEUES=8
 // hid it, which is how it was found).  So every bank type lives on a priority level of its own -- the mixers normal,
 // the Indirect models least, the LSTM (the longest stage) greatest -- and a bank's transfer streams follow its compute
-// stream's level: at most four streams per level.
+// stream's level: at most four streams per level.  The Match banks (gmx_match.inc) take the fourth place on the Indirect
+// models' level with ONE stream: their record transfers run on it too.
 static hipError_t bank_stream_create(hipStream_t* out, int level /* 0 normal, 1 least, 2 greatest */) {
   int least = 0, greatest = 0;
   hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
@@ -1512,6 +1514,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 #include "gmx_indirect.inc"
 #include "gmx_ind_ckpt.inc"
 #include "gmx_lstm.inc"
+#include "gmx_match.inc"
 #include "gmx_chainstep.inc"
 
 // ---- test probes (device math against host math; not part of the product surface) --------

@@ -74,3 +74,24 @@ def stock_indirect():
     the reference's constructor receives)."""
     import numpy as np
     return [(t, float(np.float32(lr))) for _, t, lr in STOCK_INDIRECT]
+
+
+# The six Match models of the reference in construction order (predictor.cpp:187-208 AddMatch): (context variable,
+# table_size); every one with limit 400.  Their prediction indices follow the PPM model (0), the LSTM (1), the 17
+# Indirect models of AddIndirect (2..35) and the 15 of AddSkip (36..65): predictor.cpp:17-28.
+STOCK_MATCH = [
+    ("last_byte", 1 << 8), ("last_two_bytes_hash", 1 << 16), ("last_three_bytes_hash", 1 << 24),
+    ("last_four_bytes_hash", 1 << 21), ("last_five_bytes_hash", 1 << 21), ("last_six_bytes_hash", 1 << 21),
+]
+STOCK_MATCH_LIMIT = 400
+STOCK_MATCH_SLOTS = tuple(range(66, 72))
+
+
+def stock_match():
+    """[(table_size, limit, slot)] of the six stock Match models."""
+    return [(t, STOCK_MATCH_LIMIT, s) for (_, t), s in zip(STOCK_MATCH, STOCK_MATCH_SLOTS)]
+
+
+def stock_longest_match_columns():
+    """Gate-context columns of the stock mixers that read ShortTermMemory::longest_match (6 and 30)."""
+    return [i for i, c in enumerate(stock_context_names()) if c == "longest_match"]

@@ -450,6 +450,114 @@ int gmx_lstm_import(gmx_lstm* l, int stream, const void* long_buf, size_t long_b
 int gmx_lstm_copy(gmx_lstm* dst, int dst_stream, gmx_lstm* src, int src_stream);
 int gmx_lstm_memory_usage(gmx_lstm* l, uint64_t* bytes);
 
+/* ==== Match models ============================================================================
+ * The producers of 6 of the mixers' 90 inputs and of the `longest_match` gate context: the reference's `Match`
+ * objects (models/match.h:13-45, constructed in predictor.cpp:187-208), their MatchMemory and the deduplicated input
+ * history (long-term-memory.h:42-53, :82), and the history rule of BasicContexts::Learn (basic-contexts.cpp:44-53),
+ * for S streams on one device.  One bank owns the K models of a stream, its history and its longest_match; its inputs
+ * are one context value per model and byte, and the coded bits. */
+
+/* One Match constructor call (match.h:19-21): table_size, limit, and the prediction index
+ * ShortTermMemory::AddPrediction returned (match.cpp:14-15). */
+typedef struct gmx_match_desc {
+  uint32_t table_size;
+  int32_t limit;
+  int32_t slot;
+} gmx_match_desc;
+
+typedef struct gmx_match gmx_match;
+typedef struct gmx_match_batch gmx_match_batch;
+
+/* n_models 1..8.  history_capacity: bytes of history a stream can hold (below 2^32; table entries are kept as u32).
+ * Constructed state as match.cpp:3-23.  GMX_ERR_INVALID for bad arguments, GMX_ERR_NO_DEVICE without a GPU. */
+int gmx_match_create(gmx_match** out, const gmx_match_desc* models, int n_models, uint64_t history_capacity,
+                     int n_streams, int device);
+void gmx_match_destroy(gmx_match* mb);
+int gmx_match_n_streams(const gmx_match* mb);
+int gmx_match_n_models(const gmx_match* mb);
+uint64_t gmx_match_bank_bytes(const gmx_match* mb);   /* device bytes per stream, the history buffer included */
+int gmx_match_reset(gmx_match* mb);                   /* every stream back to the constructed state */
+int gmx_match_sync(gmx_match* mb);
+int gmx_match_set_cu_mask(gmx_match* mb, const uint32_t* mask, int n_words);  /* cf. gmx_group_set_cu_mask */
+
+/* Batched surface: records {contexts[K], bit_context, bit} of up to max_bits bits per stream, results
+ * {predictions[K], active[K], longest_match} per bit.
+ *   contexts     [S][max_bits][K]  model k's aliased context variable at Predict of that bit (it does not move within
+ *                                  a byte); the kernel consumes the records of byte-opening bits (bit_context == 0)
+ *                                  and the first record of a run
+ *   bit_contexts [S][max_bits]     ShortTermMemory::bit_context, as in gmx_ind_batch
+ *   bits         [S][max_bits]
+ *   predictions  [S][max_bits][K]  what slot k of the blackboard holds after Predict (SetPrediction's logit; a model
+ *                                  that stays silent, match_length_ <= 2, leaves it as it was)
+ *   active       [S][max_bits][K]
+ *   longest      [S][max_bits]     ShortTermMemory::longest_match after the K Predicts (match.cpp:70-73) */
+int gmx_match_batch_create(gmx_match_batch** out, gmx_match* mb, uint64_t max_bits);
+void gmx_match_batch_destroy(gmx_match_batch* b);
+uint64_t gmx_match_batch_max_bits(const gmx_match_batch* b);
+uint32_t* gmx_match_batch_contexts(gmx_match_batch* b);       /* pinned host pointers, caller fills / reads */
+uint32_t* gmx_match_batch_bit_contexts(gmx_match_batch* b);
+uint8_t* gmx_match_batch_bits(gmx_match_batch* b);
+const float* gmx_match_batch_predictions(gmx_match_batch* b);
+const uint8_t* gmx_match_batch_active(gmx_match_batch* b);
+const uint32_t* gmx_match_batch_longest(gmx_match_batch* b);
+int gmx_match_batch_upload(gmx_match_batch* b, uint64_t n_bits);
+int gmx_match_batch_download(gmx_match_batch* b, uint64_t n_bits);
+int gmx_match_batch_wait(gmx_match_batch* b);                  /* cf. gmx_batch_wait */
+/* (Unlike the other banks' batches these transfers run on the bank's own stream, in order with its kernels: the bank
+ * shares a stream priority level with the Indirect banks and adds one stream to it.) */
+/* Predict AND Learn of bits [0, n_bits) of every stream, in Predictor's order (BasicContexts before the Match
+ * objects in both loops): Match::Predict changes the models' state, so there is no predict-only batch.  A run may
+ * begin and end anywhere in a byte.  `into` (nullable): a batch of a mixer group with the same number of streams on
+ * the same device, created with GMX_BATCH_MASK; the predictions are also written into its device prediction records
+ * at the models' slots, their active bits replace those slots' bits of its mask records, and longest_match is
+ * written into each of the n_ctx_columns (<= 8) gate-context columns listed in ctx_columns (the reference's
+ * topology: 6 and 30) -- ordered after what was queued on the mixer group before this call and before what is
+ * queued on it afterwards, as for gmx_indirect_run.  The coded bits are NOT copied into the mixer batch:
+ * gmx_indirect_run does that already.
+ * Capacity: the library keeps an upper bound of every stream's history size (+1 per byte a run may complete).  When
+ * a run could exceed history_capacity by that bound the true sizes are fetched from the device; if it still could,
+ * the call returns GMX_ERR_INVALID before anything is queued. */
+int gmx_match_run(gmx_match* mb, gmx_match_batch* b, uint64_t n_bits, gmx_batch* into, const int32_t* ctx_columns,
+                  int n_ctx_columns, float* kernel_ms);
+/* ... for streams at different lengths: stream s runs bits [0, n_bits[s]), 0 = it sits the launch out.  One launch. */
+int gmx_match_run_ragged(gmx_match* mb, gmx_match_batch* b, const uint64_t* n_bits /* [S] */, gmx_batch* into,
+                         const int32_t* ctx_columns, int n_ctx_columns);
+
+/* Per-bit surface, a kernel launch per call.  forward = K x Match::Predict (match.cpp:25-74) with contexts[k] = model
+ * k's aliased variable now; predictions[K] / active[K] / *longest_match (all nullable) as in the batch.  learn = the
+ * history push of BasicContexts::Learn + K x Match::Learn (match.cpp:76-109) of the bit the preceding forward
+ * predicted.  One forward per bit (GMX_ERR_STATE otherwise).  Same floats and the same state as the batched path;
+ * the two may alternate on a stream between bits. */
+int gmx_match_forward(gmx_match* mb, int stream, const uint32_t* contexts, uint32_t bit_context, float* predictions,
+                      uint8_t* active, uint32_t* longest_match);
+int gmx_match_learn(gmx_match* mb, int stream, int bit);
+
+/* What the bank carries of ShortTermMemory besides longest_match: the K blackboard slots (cf.
+ * gmx_indirect_slots_get) and new_bit, the last coded bit, which the next Match::Predict compares with the history
+ * (match.cpp:29).  Both belong to the reference's ShortTermMemory checkpoint, not to Match's: gmx_match_import leaves
+ * them alone, gmx_match_reset zeroes them, gmx_match_copy copies them.  A caller that restores a stream sets them
+ * after the import.  get: values / new_bit nullable. */
+int gmx_match_slots_get(gmx_match* mb, int stream, float* values /* [K] */, int* new_bit);
+int gmx_match_slots_set(gmx_match* mb, int stream, const float* values /* [K] */, int new_bit);
+int gmx_match_history_size(gmx_match* mb, int stream, uint64_t* size);   /* LongTermMemory::history.size() */
+
+/* Byte for byte the reference's: `long` = the history and match section of LongTermMemory::WriteToDisk
+ * (long-term-memory.cpp:70-106: u64 history size, the bytes, then per model u32 count of valid entries, {u32 key,
+ * 5 pointer bytes} in ascending key order when count < 5/9 of the table, else 5 bytes per entry, 256 floats, 256
+ * ints); `short` = Match::WriteToDisk of the K models in order (match.cpp:111-116, 11 bytes each).  Both buffers
+ * NULL: sizes only.  Valid entries are counted and packed on the device.  import validates both sections before the
+ * bank is touched -- lengths, the branch against the count, strictly ascending keys below the table size, every
+ * pointer below the imported history size with a fifth byte of 0, the history size at most the capacity, bit_pos_ 0
+ * or a power of two -- and returns GMX_ERR_FORMAT otherwise.  copy = Match::Copy and LongTermMemory::Copy's share, between
+ * banks of the same models (table sizes, limits, slots) on the same device, GMX_ERR_INVALID otherwise;
+ * memory_usage = Match::GetMemoryUsage (match.cpp:133-141). */
+int gmx_match_export(gmx_match* mb, int stream, void* long_buf, size_t* long_bytes, void* short_buf,
+                     size_t* short_bytes);
+int gmx_match_import(gmx_match* mb, int stream, const void* long_buf, size_t long_bytes, const void* short_buf,
+                     size_t short_bytes);
+int gmx_match_copy(gmx_match* dst, int dst_stream, gmx_match* src, int src_stream);
+int gmx_match_memory_usage(gmx_match* mb, int model, uint64_t* bytes);
+
 /* ==== Lock step through the whole device chain: S decoders, one device step per coded bit ======
  * The reference's Decoder (coder/decoder.cpp:19-39) learns each bit from Predict's own result, so S files being
  * restored on one GPU advance together, a bit per step (gmx_lockstep_* above does this for the mixers alone).  A
