@@ -209,8 +209,9 @@ def lib():
     L.gmx_chainstep_commit.argtypes = [vp, i32]
     L.gmx_chainstep_launch.argtypes = [vp]
     L.gmx_chainstep_wait.argtypes = [vp]
+    L.gmx_chainstep_attach_match.argtypes = [vp, vp, C.POINTER(C.c_int32), i32]
     for name in ("predictions", "active_mask", "contexts", "ind_contexts", "bit_contexts", "ppm", "bits", "what", "p",
-                 "outputs"):
+                 "outputs", "match_contexts"):
         f = getattr(L, "gmx_chainstep_" + name)
         f.argtypes = [vp]
         f.restype = vp
@@ -256,6 +257,7 @@ ABI_SYMBOLS = [
     "gmx_chainstep_active_mask", "gmx_chainstep_contexts", "gmx_chainstep_ind_contexts", "gmx_chainstep_bit_contexts",
     "gmx_chainstep_ppm", "gmx_chainstep_bits", "gmx_chainstep_what", "gmx_chainstep_p", "gmx_chainstep_outputs",
     "gmx_chainstep_commit", "gmx_chainstep_step", "gmx_chainstep_launch", "gmx_chainstep_wait",
+    "gmx_chainstep_attach_match", "gmx_chainstep_match_contexts",
     "gmx_group_set_cu_mask", "gmx_indirect_set_cu_mask", "gmx_lstm_set_cu_mask",
     "gmx_match_create", "gmx_match_destroy", "gmx_match_n_streams", "gmx_match_n_models", "gmx_match_bank_bytes",
     "gmx_match_reset", "gmx_match_sync", "gmx_match_set_cu_mask", "gmx_match_batch_create", "gmx_match_batch_destroy",

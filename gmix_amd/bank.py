@@ -397,6 +397,25 @@ class ChainStep:
         self.what = view("what", np.uint8, (S,))
         self.p = view("p", np.float32, (S,))
         self.outputs = view("outputs", np.float32, (S, M))
+        self.match_contexts = None  # (attach_match)
+
+    def _view(self, name, dtype, shape):
+        ptr = getattr(self.L, "gmx_chainstep_" + name)(self.h)
+        if not ptr:
+            return None
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return np.frombuffer((C.c_char * n).from_address(ptr), dtype=dtype).reshape(shape)
+
+    def attach_match(self, group, ctx_columns=None):
+        """The Match models of `group` (a MatchGroup of as many streams) step on the device from now on
+        (gmx_chainstep_attach_match): once, before the first step.  Afterwards `match_contexts` [S][K] takes the models'
+        context words (byte-opening predicts and a stream's first predict), `bit_contexts` every predict's."""
+        cols = [int(c) for c in (ctx_columns or [])]
+        arr = (C.c_int32 * max(1, len(cols)))(*cols)
+        check(self.L.gmx_chainstep_attach_match(self.h, group.h, arr, len(cols)), "gmx_chainstep_attach_match")
+        self.match_contexts = self._view("match_contexts", np.uint32, (self.g.S, group.K))
+        if self.bit_contexts is None:
+            self.bit_contexts = self._view("bit_contexts", np.uint32, (self.g.S,))
 
     def set_active(self, stream, active):
         """active[N] flags -> the stream's mask words."""

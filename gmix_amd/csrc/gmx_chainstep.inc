@@ -13,6 +13,12 @@
 //                     opens a byte, LstmModel::Predict's range walk for the bit, Indirect::Predict x K on the caller's
 //                     contexts, Mixer::Predict x M on the caller's record with the device-side models' slots filled in
 //
+// With a Match bank attached (gmx_chainstep_attach_match) a step is also the history push of BasicContexts::Learn and
+// Match::Learn x K, then Match::Predict x K, of every stream that asks (gmx_match_step.h): in lanes 56..63 of the Indirect
+// models' launch, or -- without Indirect models, or with more than 56 -- in gmx_match_step_kernel in front of the mixers'.
+// Then 89 of the 90 inputs and the gate contexts of mixers 6 and 30 never leave the device; the host supplies the bit
+// context per predict and the models' context words per byte-opening predict.
+//
 // as ONE hipGraph of kernels only.  No copy node: a graph's small memcpy nodes cost 9-11 us EACH on this part
 // (scripts/trace_chainstep.sh: three uploads and a download were 35 of a step's 53 us).
 //
@@ -46,11 +52,22 @@ extern "C" hipError_t gmx_launch_stock_step(const GmxTopoDev* tp_dev, const GmxS
                                             hipStream_t stream);
 extern "C" hipError_t gmx_launch_models_step(const GmxIndDev* dv, const GmxIndStepArgs* args, const GmxLstmDev* ldv,
                                              const GmxLstmBitArgs* largs, int n_streams, hipStream_t stream);
+extern "C" hipError_t gmx_launch_models_step_match(const GmxIndDev* dv, int k_ind, const GmxIndStepArgs* args,
+                                                   const GmxLstmDev* ldv, const GmxLstmBitArgs* largs,
+                                                   const GmxMatchDev* mdv, const GmxMatchStepArgs* margs, int n_streams,
+                                                   hipStream_t stream);
+extern "C" hipError_t gmx_launch_match_step(const GmxMatchDev* dv, const GmxMatchStepArgs* args, hipStream_t stream);
 
 struct gmx_chainstep {
   gmx_group* g = nullptr;
   gmx_indirect* ib = nullptr;
   gmx_lstm* l = nullptr;
+  gmx_match* mb = nullptr;         // gmx_chainstep_attach_match: the Match models step on the device too
+  int n_mcols = 0;                 // mixer context columns that receive longest_match
+  int32_t mcols[GMX_MATCH_MAX_CTX_COLS] = {};
+  uint32_t* mctx = nullptr;        // host view [S][K_match]: the Match models' context words (room for 8 a stream)
+  std::vector<uint32_t> m_bc;      // bit_context of the stream's outstanding Predict (does its Learn complete a byte?)
+  std::vector<uint8_t> m_seen;     // the stream has predicted through this object (its first Predict reads mctx)
   int S = 0, lstm_slot = -1, mixer_ctx_col = -1, ind_ctx_col = -1;
   // h_in: ONE pinned host block [control words | records], uploaded by the step's first kernel into d_in[parity];
   // h_bd: what a byte-opening step adds (PPM distributions, the bytes just completed, the LSTM's counts) -> d_bd;
@@ -192,6 +209,27 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
       ba.ind_ctx_col = cs->ind_ctx_col;
     }
   }
+  GmxMatchStepArgs ma;
+  memset(&ma, 0, sizeof ma);
+  // the Match lanes ride in the Indirect models' launch where its wave has the eight lanes to spare
+  const bool m_fused = cs->mb && cs->ib && cs->ib->dev.k <= 56 && t.mask_words <= 8;
+  if (cs->mb) {
+    ma.banks = cs->mb->banks;
+    ma.hist = cs->mb->hist;
+    ma.ctx = (const uint32_t*)cur(cs->mctx);
+    ma.bc = (const uint32_t*)cur(cs->ibc);
+    ma.bits = bits_d;
+    ma.what = what_d;
+    ma.mx_pred = pred_d;
+    ma.mx_mask = mask_d;
+    ma.mx_ctx = ctx_d;
+    ma.mx_n_pad = t.n_pad;
+    ma.mx_mask_words = t.mask_words;
+    ma.mx_m = t.m;
+    ma.n_ctx_cols = cs->n_mcols;
+    for (int c = 0; c < cs->n_mcols; ++c) ma.ctx_cols[c] = cs->mcols[c];
+    ma.n_streams = cs->S;
+  }
   if (cs->ib && cs->l) {
     // the LSTM's bit prediction and the Indirect models in one launch, the step's inputs fetched by it
     GmxIndStepArgs ia;
@@ -207,7 +245,9 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
     ia.mx_n_pad = t.n_pad;
     ia.mx_mask_words = t.mask_words;
     ia.up = up;
-    e = gmx_launch_models_step(cs->ib->dev_d, &ia, cs->l->dev_d, &ba, cs->S, st);
+    e = m_fused ? gmx_launch_models_step_match(cs->ib->dev_d, cs->ib->dev.k, &ia, cs->l->dev_d, &ba, cs->mb->dev_d, &ma,
+                                               cs->S, st)
+                : gmx_launch_models_step(cs->ib->dev_d, &ia, cs->l->dev_d, &ba, cs->S, st);
     if (e != hipSuccess) return e;
   } else {
     if (up.n > 0) {
@@ -227,12 +267,18 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
       ia.mx_mask = mask_d;
       ia.mx_n_pad = t.n_pad;
       ia.mx_mask_words = t.mask_words;
-      e = gmx_launch_indirect_step(cs->ib->dev_d, &ia, cs->S, st);
+      e = m_fused ? gmx_launch_models_step_match(cs->ib->dev_d, cs->ib->dev.k, &ia, nullptr, nullptr, cs->mb->dev_d, &ma,
+                                                 cs->S, st)
+                  : gmx_launch_indirect_step(cs->ib->dev_d, &ia, cs->S, st);
       if (e != hipSuccess) return e;
     } else if (cs->l) {
       e = gmx_launch_lstm_bitstep(cs->l->dev_d, &ba, cs->S, st);
       if (e != hipSuccess) return e;
     }
+  }
+  if (cs->mb && !m_fused) {  // one node of their own in front of the mixers' (gmx_match_step_kernel)
+    e = gmx_launch_match_step(cs->mb->dev_d, &ma, st);
+    if (e != hipSuccess) return e;
   }
   if (cs->stock) {
     // Mixer::Learn x M of the streams that ask, on the records of their forward -- the step before's, in the other
@@ -284,6 +330,36 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
   a.mode = GMX_MODE_PREDICT | GMX_MODE_LATCH | (g->stock_exact ? GMX_MODE_EXACT : 0u);
   a.T_list = (const uint64_t*)cur(cs->tl_pred);
   return lockstep_launch_kernel(g, a, st);
+}
+
+// The four graphs (parity x opens a byte; two without an LSTM), dropping the ones there are.
+static hipError_t cs_capture(gmx_chainstep* cs) {
+  hipStream_t st = cs->g->stream;
+  for (int par = 0; par < 2; ++par)
+    for (int opens = 0; opens < 2; ++opens) {
+      if (cs->exec[par][opens]) (void)hipGraphExecDestroy(cs->exec[par][opens]);
+      if (cs->graph[par][opens]) (void)hipGraphDestroy(cs->graph[par][opens]);
+      cs->exec[par][opens] = nullptr;
+      cs->graph[par][opens] = nullptr;
+    }
+  // once outside a capture, with every stream sitting out (all counts and flags are zero): whatever a launcher
+  // sets up on its first call (dynamic LDS limits) is set up
+  hipError_t e = cs_record(cs, st, true, 0);
+  if (e != hipSuccess) return e;
+  e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return e;
+  for (int par = 0; par < 2; ++par)
+    for (int opens = 0; opens < (cs->l ? 2 : 1); ++opens) {
+      e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+      if (e != hipSuccess) return e;
+      e = cs_record(cs, st, opens != 0, par);
+      const hipError_t e2 = hipStreamEndCapture(st, &cs->graph[par][opens]);
+      if (e != hipSuccess) return e;
+      if (e2 != hipSuccess) return e2;
+      e = hipGraphInstantiate(&cs->exec[par][opens], cs->graph[par][opens], nullptr, nullptr, 0);
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
 }
 
 extern "C" int gmx_chainstep_create(gmx_chainstep** out, gmx_group* g, gmx_indirect* ib, gmx_lstm* l, int lstm_slot,
@@ -344,6 +420,8 @@ extern "C" int gmx_chainstep_create(gmx_chainstep** out, gmx_group* g, gmx_indir
                c_tlp = take(S * 8), c_seq = take(S * 4);
   const size_t r_pred = take(S * t.n_pad * 4), r_mask = take(S * t.mask_words * 4), r_ctx = take(S * t.m * 4),
                r_ictx = take((K ? S * K : 1) * 4), r_ibc = take(S * 4);
+  // (room for an attached Match bank's context words: the block and the host views never move)
+  const size_t r_mctx = take(S * GMX_MATCH_MAX_MODELS * 4);
   cs->in_bytes = o;
   {
     const size_t offs[] = {c_bits, c_whatd, c_dec, c_seq, c_tll, c_tlp, r_pred, r_mask, r_ctx, r_ictx, r_ibc};
@@ -414,6 +492,7 @@ extern "C" int gmx_chainstep_create(gmx_chainstep** out, gmx_group* g, gmx_indir
   cs->ctx = (uint32_t*)(cs->h_in + r_ctx);
   cs->ictx = (uint32_t*)(cs->h_in + r_ictx);
   cs->ibc = (uint32_t*)(cs->h_in + r_ibc);
+  cs->mctx = (uint32_t*)(cs->h_in + r_mctx);
   cs->ppm = (float*)(cs->h_bd + b_ppm);
   cs->bytes = cs->h_bd + b_bytes;
   cs->nl_perceive = (uint64_t*)(cs->h_bd + b_nlp);
@@ -440,20 +519,7 @@ extern "C" int gmx_chainstep_create(gmx_chainstep** out, gmx_group* g, gmx_indir
   cs->pending.assign(S, 0);
   cs->nbits.assign(S, 0);
   cs->acc.assign(S, 0);
-  hipStream_t st = g->stream;
-  // once outside a capture, with every stream sitting out (all counts and flags are zero): whatever a launcher
-  // sets up on its first call (dynamic LDS limits) is set up
-  CCHK(cs_record(cs, st, true, 0));
-  CCHK(hipStreamSynchronize(st));
-  for (int par = 0; par < 2; ++par)
-    for (int opens = 0; opens < (l ? 2 : 1); ++opens) {
-      CCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      hipError_t e = cs_record(cs, st, opens != 0, par);
-      hipError_t e2 = hipStreamEndCapture(st, &cs->graph[par][opens]);
-      CCHK(e);
-      CCHK(e2);
-      CCHK(hipGraphInstantiate(&cs->exec[par][opens], cs->graph[par][opens], nullptr, nullptr, 0));
-    }
+  CCHK(cs_capture(cs));
 #undef CCHK
   *out = cs;
   return GMX_OK;
@@ -464,7 +530,46 @@ extern "C" float* gmx_chainstep_predictions(gmx_chainstep* cs) { return cs ? cs-
 extern "C" uint32_t* gmx_chainstep_active_mask(gmx_chainstep* cs) { return cs ? cs->mask : nullptr; }
 extern "C" uint32_t* gmx_chainstep_contexts(gmx_chainstep* cs) { return cs ? cs->ctx : nullptr; }
 extern "C" uint32_t* gmx_chainstep_ind_contexts(gmx_chainstep* cs) { return (cs && cs->ib) ? cs->ictx : nullptr; }
-extern "C" uint32_t* gmx_chainstep_bit_contexts(gmx_chainstep* cs) { return (cs && cs->ib) ? cs->ibc : nullptr; }
+extern "C" uint32_t* gmx_chainstep_bit_contexts(gmx_chainstep* cs) { return (cs && (cs->ib || cs->mb)) ? cs->ibc : nullptr; }
+extern "C" uint32_t* gmx_chainstep_match_contexts(gmx_chainstep* cs) { return (cs && cs->mb) ? cs->mctx : nullptr; }
+
+// The Match models of every stream step on the device from now on (gmx_match_step.h): their slots of the mixers'
+// record, their mask bits and longest_match in the listed gate-context columns are the device's; the host supplies
+// match_contexts[s][K] on byte-opening predicts and on a stream's first predict, and bit_contexts[s] on every one.
+extern "C" int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, const int32_t* ctx_columns,
+                                          int n_ctx_columns) {
+  if (!cs || !cs->g || !mb) return GMX_ERR_INVALID;
+  if (cs->mb || cs->steps != 0 || cs->in_flight) return GMX_ERR_STATE;  // once, before the first step
+  gmx_group* g = cs->g;
+  const GmxTopoDev& t = g->topo;
+  if (mb->S != cs->S || mb->device != g->device || t.mask_words > GMX_MATCH_MAX_MASK_WORDS) return GMX_ERR_INVALID;
+  if (n_ctx_columns < 0 || n_ctx_columns > GMX_MATCH_MAX_CTX_COLS || (n_ctx_columns > 0 && !ctx_columns))
+    return GMX_ERR_INVALID;
+  for (int c = 0; c < n_ctx_columns; ++c)
+    if (ctx_columns[c] < 0 || ctx_columns[c] >= t.m) return GMX_ERR_INVALID;
+  for (int i = 0; i < mb->dev.k; ++i)
+    if (mb->dev.m[i].slot < 0 || mb->dev.m[i].slot >= t.n) return GMX_ERR_INVALID;
+  if (cs->up.n >= GMX_STEP_UP_MAX) return GMX_ERR_INVALID;
+  HIPCHK(hipSetDevice(g->device));
+  HIPCHK(hipStreamSynchronize(mb->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));
+  cs->mb = mb;
+  cs->n_mcols = n_ctx_columns;
+  for (int c = 0; c < n_ctx_columns; ++c) cs->mcols[c] = ctx_columns[c];
+  cs->m_bc.assign(cs->S, 0);
+  cs->m_seen.assign(cs->S, 0);
+  // the context words join the records of a step: gmx_chainstep_commit and the upload slices move them
+  cs->up.off[cs->up.n] = (uint32_t)((const uint8_t*)cs->mctx - cs->h_in);
+  cs->up.bps[cs->up.n] = (uint32_t)mb->dev.k * 4u;
+  cs->up.n += 1;
+  const hipError_t e = cs_capture(cs);
+  if (e != hipSuccess) {  // (the object cannot step any more: no graph of it is whole)
+    cs->mb = nullptr;
+    cs->up.n -= 1;
+    return e == hipErrorOutOfMemory ? GMX_ERR_NOMEM : hip_fail(e, "gmx_chainstep_attach_match: capture");
+  }
+  return GMX_OK;
+}
 extern "C" float* gmx_chainstep_ppm(gmx_chainstep* cs) { return (cs && cs->l) ? cs->ppm : nullptr; }
 extern "C" uint8_t* gmx_chainstep_bits(gmx_chainstep* cs) { return cs ? cs->bits : nullptr; }
 extern "C" uint8_t* gmx_chainstep_what(gmx_chainstep* cs) { return cs ? cs->what : nullptr; }
@@ -541,6 +646,16 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
   for (int s = 0; s < S; ++s)  // (its record is in the device copy the NEXT step learns from, and only that one)
     if (cs->pending[s] && !(cs->what[s] & GMX_STEP_LEARN)) return GMX_ERR_STATE;
   HIPCHK(hipSetDevice(g->device));
+  if (cs->mb) {
+    // a history grows by one byte per stream whose Learn completes a byte: the rule of gmx_match_run -- when a bound
+    // could pass the capacity the true sizes are fetched, and if it still could nothing is queued
+    std::vector<uint64_t> add(S, 0);
+    for (int s = 0; s < S; ++s) add[s] = ((cs->what[s] & GMX_STEP_LEARN) && cs->m_bc[s] >= 127u) ? 1 : 0;
+    int rc = match_reserve(cs->mb, 0, S, add.data());
+    if (rc) return rc;
+    if (hipStreamQuery(cs->mb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(cs->mb->stream));
+    (void)hipGetLastError();
+  }
   {  // nobody else holds rows or table entries in registers, nothing of the banks' own is still in flight
     int rc = sessions_close(g, false);
     if (rc) return rc;
@@ -590,6 +705,11 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
       cs->nl_forward[s] = 1;
       opens = opens || cs->l != nullptr;
     }
+    if (cs->mb && (w & GMX_STEP_PREDICT)) {
+      if (!cs->m_seen[s]) wd |= 8u;  // the stream's first Predict here: its context words are read wherever in a byte it is
+      cs->m_seen[s] = 1;
+      cs->m_bc[s] = cs->ibc[s];
+    }
     cs->what_dev[s] = wd;
   }
   cs->seq_no += 1;
@@ -623,6 +743,7 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
     if (w) {
       g->fwd_done[s] = 0;
       if (cs->ib) cs->ib->fwd_done[s] = 0;
+      if (cs->mb) cs->mb->fwd_done[s] = 0;
       if (cs->l) {
         cs->l->fwd_done[s] = 0;
         cs->l->range_read[s].valid = false;

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "gmx_internal.h"
+#include "gmx_match_step.h"
 #include "gmx_math.h"
 #include "gmx_step_dev.h"
 
@@ -659,10 +660,14 @@ extern "C" hipError_t gmx_launch_indirect_init(uint8_t* banks, uint64_t bank_byt
 // of the 82 KiB of tables for one bit's work).  Predictions go straight into the mixers' records of the same step.
 // WITH_LSTM: the LSTM's bit prediction of the same step (gmx_step_dev.h) first, in the same launch -- a launch of its
 // own cost the step 4.5 us for 0.5 us of work; lstm_prediction_context reaches the model that reads it through LDS.
-template <bool WITH_LSTM>
+// WITH_MATCH: the stream's Match models (gmx_match_step.h) in lanes 56..63 of the same wave -- idle otherwise (the
+// launcher's callers see to K <= 56), and exactly one DPP group of eight.  Their loads ride in the three trips below:
+// state and record with trip 1; both probabilities, the count and the table entry with trip 2; the history byte with
+// trip 3; their stores go out behind the Indirect models'.  Their active bits join the wave's mask words in LDS.
+template <bool WITH_LSTM, bool WITH_MATCH>
 __global__ void __launch_bounds__(64)
 gmx_indirect_step_kernel(const GmxIndDev* __restrict__ dv, const GmxIndStepArgs a, const GmxLstmDev* __restrict__ ldv,
-                         const GmxLstmBitArgs la) {
+                         const GmxLstmBitArgs la, const GmxMatchDev* __restrict__ mdv, const GmxMatchStepArgs ma) {
   __shared__ uint64_t s_tab[32];
   __shared__ uint8_t nsn[512], rmn[512];
   __shared__ uint32_t mwl[8];
@@ -710,6 +715,8 @@ gmx_indirect_step_kernel(const GmxIndDev* __restrict__ dv, const GmxIndStepArgs 
     va = slots[2 * lane];
     vb = slots[2 * lane + 1];
   }
+  GmxMatchStepLane mt;
+  if (WITH_MATCH) gmx_match_step_begin(mt, mdv, ma, s, lane - 56, lane >= 56, what);
   if (!(what & 3u)) return;  // the stream sits the step out
   const bool do_pred = (what & 2u) != 0;
   const bool with_lstm = WITH_LSTM && do_pred;
@@ -728,12 +735,14 @@ gmx_indirect_step_kernel(const GmxIndDev* __restrict__ dv, const GmxIndStepArgs 
     idx = ((ctx << 8) + bcu) % d.size;  // indirect.cpp:31-32, 32-bit wrap
     e = tab[idx];
   }
+  if (WITH_MATCH) gmx_match_step_fetch(mt);
   __syncthreads();  // (the tables and the distribution are in LDS)
   if (with_lstm) {  // ... while those are on their way: lane 0's walk down the distribution
     uint32_t act;
     gmx_lstm_bitstep_walk(ldv, la, s, what, lstm_ctx, pr, lane, /*mask_to_global=*/false, act);
     if (lane == 0 && act) atomicOr(&mwl[la.slot >> 5], 1u << (la.slot & 31));  // (the host left the slot's bit clear)
   }
+  if (WITH_MATCH) gmx_match_step_look(mt);  // (its history byte travels with trip 3 below)
   if (on) {
     float na = 0.f, nb = 0.f;
     uint32_t e_upd = 0;
@@ -778,6 +787,10 @@ gmx_indirect_step_kernel(const GmxIndDev* __restrict__ dv, const GmxIndStepArgs 
     L[1] = e;
     L[2] = have;
   }
+  if (WITH_MATCH) {
+    gmx_match_step_finish(mt, ma, s);
+    if (mt.active) atomicOr(&mwl[(uint32_t)mt.md.slot >> 5], 1u << ((uint32_t)mt.md.slot & 31u));
+  }
   __syncthreads();
   // the mask words of the mixers' record: the host left the models' bits clear
   if ((what & 2u) && a.mx_mask && lane < a.mx_mask_words && lane < 8)
@@ -789,14 +802,39 @@ extern "C" hipError_t gmx_launch_indirect_step(const GmxIndDev* dv, const GmxInd
   (void)hipGetLastError();
   GmxLstmBitArgs none;
   memset(&none, 0, sizeof none);
-  hipLaunchKernelGGL(gmx_indirect_step_kernel<false>, dim3(n_streams), dim3(64), 0, stream, dv, *args,
-                     (const GmxLstmDev*)nullptr, none);
+  GmxMatchStepArgs mnone;
+  memset(&mnone, 0, sizeof mnone);
+  hipLaunchKernelGGL((gmx_indirect_step_kernel<false, false>), dim3(n_streams), dim3(64), 0, stream, dv, *args,
+                     (const GmxLstmDev*)nullptr, none, (const GmxMatchDev*)nullptr, mnone);
   return hipGetLastError();
 }
 // ... with the LSTM's bit prediction of the same step in front
 extern "C" hipError_t gmx_launch_models_step(const GmxIndDev* dv, const GmxIndStepArgs* args, const GmxLstmDev* ldv,
                                              const GmxLstmBitArgs* largs, int n_streams, hipStream_t stream) {
   (void)hipGetLastError();
-  hipLaunchKernelGGL(gmx_indirect_step_kernel<true>, dim3(n_streams), dim3(64), 0, stream, dv, *args, ldv, *largs);
+  GmxMatchStepArgs mnone;
+  memset(&mnone, 0, sizeof mnone);
+  hipLaunchKernelGGL((gmx_indirect_step_kernel<true, false>), dim3(n_streams), dim3(64), 0, stream, dv, *args, ldv, *largs,
+                     (const GmxMatchDev*)nullptr, mnone);
+  return hipGetLastError();
+}
+// ... and with the stream's Match models in lanes 56..63 (ldv null: no LSTM).  k_ind <= 56 and at most 8 mask words
+// are the caller's to see to (gmx_chainstep.inc); checked here all the same.
+extern "C" hipError_t gmx_launch_models_step_match(const GmxIndDev* dv, int k_ind, const GmxIndStepArgs* args,
+                                                   const GmxLstmDev* ldv, const GmxLstmBitArgs* largs,
+                                                   const GmxMatchDev* mdv, const GmxMatchStepArgs* margs, int n_streams,
+                                                   hipStream_t stream) {
+  (void)hipGetLastError();
+  if (k_ind > 56 || !mdv || !margs || args->mx_mask_words < 1 || args->mx_mask_words > 8 || !args->mx_mask)
+    return hipErrorInvalidValue;
+  if (ldv) {
+    hipLaunchKernelGGL((gmx_indirect_step_kernel<true, true>), dim3(n_streams), dim3(64), 0, stream, dv, *args, ldv,
+                       *largs, mdv, *margs);
+  } else {
+    GmxLstmBitArgs none;
+    memset(&none, 0, sizeof none);
+    hipLaunchKernelGGL((gmx_indirect_step_kernel<false, true>), dim3(n_streams), dim3(64), 0, stream, dv, *args,
+                       (const GmxLstmDev*)nullptr, none, mdv, *margs);
+  }
   return hipGetLastError();
 }

@@ -76,6 +76,24 @@ struct GmxMatchRunArgs {
   int32_t ctx_cols[GMX_MATCH_MAX_CTX_COLS];
 };
 
+// One bit of every stream in lock step, the coded bit of a forward known a launch later (gmx_match_step.h; hosted by
+// gmx_match_step_kernel and by gmx_indirect_step_kernel, gmx_chainstep.inc)
+struct GmxMatchStepArgs {
+  uint8_t* banks;
+  uint8_t* hist;              // [S][hist_cap]
+  const uint32_t* ctx;        // [S][k]  read when the step's Predict opens a byte, or what[s] & 8
+  const uint32_t* bc;         // [S]     bit_context of this step's Predict
+  const uint8_t* bits;        // [S]     the coded bit of each stream's previous forward
+  const uint8_t* what;        // [S]     bit 0: learn, bit 1: predict, bit 3: read ctx whatever bc; 0: sits out
+  float* mx_pred;             // [S][mx_n_pad] the mixers' records of the same step
+  uint32_t* mx_mask;          // [S][mx_mask_words]
+  uint32_t* mx_ctx;           // [S][mx_m]
+  int32_t mx_n_pad, mx_mask_words, mx_m;
+  int32_t n_ctx_cols;
+  int32_t ctx_cols[GMX_MATCH_MAX_CTX_COLS];
+  int32_t n_streams;
+};
+
 // ---- checkpoint (long-term-memory.cpp:70-106) -------------------------------------------------------------
 // A table is walked in chunks of GMX_MATCH_CKPT_CHUNK entries, one block per chunk: the six stock tables are
 // 1 412 chunks.  An entry is valid when it is not 0 (its fifth byte is always 0 here).

@@ -31,20 +31,8 @@
 #include <stdint.h>
 
 #include "gmx_match.h"
+#include "gmx_match_step.h"
 #include "gmx_math.h"
-
-// max / or over the eight lanes of a group (lanes 8g .. 8g+7 of a row of 16): xor 1, xor 2 by quad_perm, then the
-// other quad by row_half_mirror.  Every lane of the wave must be executing.
-template <bool OR>
-__device__ __forceinline__ uint32_t gmx_match_grp8(uint32_t v) {
-  uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
-  v = OR ? (v | o) : (v > o ? v : o);
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);           // quad_perm [2,3,0,1]
-  v = OR ? (v | o) : (v > o ? v : o);
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false);          // row_half_mirror
-  v = OR ? (v | o) : (v > o ? v : o);
-  return v;
-}
 
 __global__ void __launch_bounds__(64) gmx_match_kernel(const GmxMatchDev* __restrict__ dv, const GmxMatchRunArgs a) {
   const int lane = (int)threadIdx.x;
@@ -252,6 +240,30 @@ __global__ void __launch_bounds__(64) gmx_match_kernel(const GmxMatchDev* __rest
   }
 }
 
+// One lock-step bit of every stream (gmx_chainstep.inc) where the Indirect models' step kernel cannot carry the Match
+// lanes (no Indirect models, or more than 56 of them): gmx_match_step.h's group of eight lanes, eight streams per wave
+// as above, one node of the step's graph in front of the mixers' kernel.  The mask words of the mixers' record are
+// read-modify-written in place: nobody else writes them in this node (the LSTM's bit step ran in an earlier one), and
+// the host left the models' bits clear.
+__global__ void __launch_bounds__(64) gmx_match_step_kernel(const GmxMatchDev* __restrict__ dv, const GmxMatchStepArgs a) {
+  const int lane = (int)threadIdx.x;
+  const int k = lane & 7;
+  const int s = (int)blockIdx.x * 8 + (lane >> 3);
+  const bool in_range = s < a.n_streams && k < dv->k;
+  const uint32_t what = in_range ? a.what[s] : 0u;
+  GmxMatchStepLane m;
+  gmx_match_step_begin(m, dv, a, s, k, in_range, what);
+  gmx_match_step_fetch(m);
+  gmx_match_step_look(m);
+  gmx_match_step_finish(m, a, s);
+  const int MW = a.mx_mask_words;  // (uniform)
+  const uint32_t my_word = (uint32_t)m.md.slot >> 5, my_bit = 1u << ((uint32_t)m.md.slot & 31u);
+  for (int w = 0; w < MW; ++w) {
+    const uint32_t set = gmx_match_grp8<true>(m.active && my_word == (uint32_t)w ? my_bit : 0u);
+    if (m.lead && m.do_pred && set) a.mx_mask[(uint64_t)s * (uint64_t)MW + w] |= set;
+  }
+}
+
 // Constructed state (match.cpp:3-23, long-term-memory.h:42-53): tables zero, predictions[i] =
 // float(0.5 + (i + 0.5) / 512) computed in double, counts 1, bit_pos_ 128, everything else 0.
 // grid: x = blocks striding over the bank, y = stream
@@ -398,6 +410,15 @@ extern "C" hipError_t gmx_launch_match_kernel(const GmxMatchDev* dv, const GmxMa
   if (args->mx_pred && (args->mx_mask_words < 1 || args->mx_mask_words > GMX_MATCH_MAX_MASK_WORDS))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(gmx_match_kernel, dim3((unsigned)((args->n_streams + 7) / 8)), dim3(64), 0, stream, dv, *args);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t gmx_launch_match_step(const GmxMatchDev* dv, const GmxMatchStepArgs* args, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (args->n_streams < 1 || args->mx_mask_words < 1 || args->mx_mask_words > GMX_MATCH_MAX_MASK_WORDS)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gmx_match_step_kernel, dim3((unsigned)((args->n_streams + 7) / 8)), dim3(64), 0, stream, dv,
+                     *args);
   return hipGetLastError();
 }
 

@@ -596,7 +596,7 @@ float* gmx_chainstep_predictions(gmx_chainstep* cs);     /* pinned host [S][n_pa
 uint32_t* gmx_chainstep_active_mask(gmx_chainstep* cs);  /* [S][mask_words] */
 uint32_t* gmx_chainstep_contexts(gmx_chainstep* cs);     /* [S][M] */
 uint32_t* gmx_chainstep_ind_contexts(gmx_chainstep* cs); /* [S][K]; NULL without Indirect models */
-uint32_t* gmx_chainstep_bit_contexts(gmx_chainstep* cs); /* [S] */
+uint32_t* gmx_chainstep_bit_contexts(gmx_chainstep* cs); /* [S]; NULL without Indirect models and Match bank */
 float* gmx_chainstep_ppm(gmx_chainstep* cs);             /* [S][256]; NULL without an LSTM */
 uint8_t* gmx_chainstep_bits(gmx_chainstep* cs);          /* [S] */
 uint8_t* gmx_chainstep_what(gmx_chainstep* cs);          /* [S] GMX_STEP_* */
@@ -606,6 +606,21 @@ int gmx_chainstep_commit(gmx_chainstep* cs, int stream);
 int gmx_chainstep_step(gmx_chainstep* cs);
 int gmx_chainstep_launch(gmx_chainstep* cs);
 int gmx_chainstep_wait(gmx_chainstep* cs);
+/* gmx_chainstep_attach_match: the Match models of every stream (a gmx_match bank of the same stream count on the same
+ * device) step on the device as well: per step the history push of BasicContexts::Learn and K x Match::Learn, then
+ * K x Match::Predict -- in idle lanes of the Indirect models' launch where there are Indirect models (at most 56) and a
+ * mask of at most 8 words, in a launch of their own in front of the mixers' otherwise.  Their slots of predictions[s], their
+ * bits of active_mask[s] (left clear by the caller) and longest_match in the gate-context columns ctx_columns[] (at most
+ * 8) are the device's.  The caller fills bit_contexts[s] on every GMX_STEP_PREDICT and match_contexts[s][K] -- the
+ * models' aliased context variables -- on predicts that open a byte (bit_contexts[s] == 0) and on a stream's first
+ * predict through this object; streams need not start at a byte boundary.  Once, before the object's first step
+ * (GMX_ERR_STATE otherwise); GMX_ERR_INVALID for another stream count or device, a model slot outside [0, n), a column
+ * outside [0, M), more than 8 columns.  Nothing is kept outside the bank: between steps (and after the object is
+ * destroyed) its streams may go on through gmx_match_run or gmx_match_forward / _learn, a pending gmx_match_forward
+ * being dropped by a step as by a batch.  A step that could take a history past history_capacity returns
+ * GMX_ERR_INVALID before anything is queued (the rule of gmx_match_run). */
+int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, const int32_t* ctx_columns, int n_ctx_columns);
+uint32_t* gmx_chainstep_match_contexts(gmx_chainstep* cs);   /* pinned host [S][K_match]; NULL before attach */
 
 /* ==== Compute-unit shares ======================================================================
  * A bank's kernels normally spread over the whole chip.  Kernels of DIFFERENT banks that cannot share
