@@ -191,6 +191,8 @@ def lib():
     L.gmx_match_export.argtypes = [vp, i32, vp, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_size_t)]
     L.gmx_match_import.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.gmx_match_copy.argtypes = [vp, i32, vp, i32]
+    L.gmx_match_group_export.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+    L.gmx_match_group_import.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_size_t), vp]
     L.gmx_match_memory_usage.argtypes = [vp, i32, C.POINTER(u64)]
     L.gmx_lockstep_create.argtypes = [C.POINTER(vp), vp, C.c_uint]
     L.gmx_lockstep_destroy.argtypes = [vp]
@@ -265,5 +267,5 @@ ABI_SYMBOLS = [
     "gmx_match_batch_predictions", "gmx_match_batch_active", "gmx_match_batch_longest", "gmx_match_batch_upload",
     "gmx_match_batch_download", "gmx_match_batch_wait", "gmx_match_run", "gmx_match_run_ragged", "gmx_match_forward",
     "gmx_match_learn", "gmx_match_slots_get", "gmx_match_slots_set", "gmx_match_history_size", "gmx_match_export",
-    "gmx_match_import", "gmx_match_copy", "gmx_match_memory_usage",
+    "gmx_match_import", "gmx_match_copy", "gmx_match_memory_usage", "gmx_match_group_export", "gmx_match_group_import",
 ]

@@ -46,6 +46,7 @@ struct gmx_match {
   uint32_t* model_cnt_d = nullptr;
   uint8_t* model_dense_d = nullptr;
   uint64_t* model_off_d = nullptr;
+  uint64_t gck_ops = 0;  // launches, transfers, synchronisations, allocations of the group checkpoint calls so far
 };
 
 extern "C" {
@@ -709,14 +710,20 @@ out:
   return ret;
 }
 
-extern "C" int gmx_match_import(gmx_match* mb, int stream, const void* long_buf, size_t long_bytes,
-                                const void* short_buf, size_t short_bytes) {
-  if (!mb || stream < 0 || stream >= mb->S || !long_buf || !short_buf) return GMX_ERR_INVALID;
-  const GmxMatchDev& d = mb->dev;
+// What gmx_match_import and gmx_match_group_import demand of one stream's two sections, and where its parts lie.
+struct GmxMatchSection {
+  uint64_t hs = 0;                               // history size
+  const uint8_t* hist_src = nullptr;
+  uint32_t cnt[GMX_MATCH_MAX_MODELS] = {};
+  uint8_t dense[GMX_MATCH_MAX_MODELS] = {};
+  uint64_t moff[GMX_MATCH_MAX_MODELS] = {};      // byte offset of a model's body (behind its count) in the section
+  const uint8_t* tail[GMX_MATCH_MAX_MODELS] = {};
+  uint64_t cms[GMX_MATCH_MAX_MODELS] = {};       // cur_match_ of the short section
+};
+static int match_validate_section(const GmxMatchDev& d, const uint8_t* lb, size_t long_bytes, const uint8_t* sb,
+                                  size_t short_bytes, GmxMatchSection* out) {
   const int K = d.k;
-  // ---- validate everything before the bank is touched
   if (short_bytes != 11 * (size_t)K) return GMX_ERR_FORMAT;
-  const uint8_t* const lb = (const uint8_t*)long_buf;
   const uint8_t* p = lb;
   const uint8_t* const end = p + long_bytes;
   if (end - p < 8) return GMX_ERR_FORMAT;
@@ -724,12 +731,11 @@ extern "C" int gmx_match_import(gmx_match* mb, int stream, const void* long_buf,
   memcpy(&hs, p, 8);
   p += 8;
   if (hs > d.hist_cap || (uint64_t)(end - p) < hs) return GMX_ERR_FORMAT;
-  const uint8_t* const hist_src = p;
+  out->hs = hs;
+  out->hist_src = p;
   p += hs;
-  uint32_t cnt[GMX_MATCH_MAX_MODELS] = {};
-  uint8_t dense[GMX_MATCH_MAX_MODELS] = {};
-  uint64_t moff[GMX_MATCH_MAX_MODELS] = {};
-  const uint8_t* tail[GMX_MATCH_MAX_MODELS] = {};
+  uint32_t* const cnt = out->cnt;
+  uint8_t* const dense = out->dense;
   for (int i = 0; i < K; ++i) {
     const uint32_t size = d.m[i].table_size;
     if (end - p < 4) return GMX_ERR_FORMAT;
@@ -737,7 +743,7 @@ extern "C" int gmx_match_import(gmx_match* mb, int stream, const void* long_buf,
     p += 4;
     if (cnt[i] > size) return GMX_ERR_FORMAT;
     dense[i] = match_is_dense(cnt[i], size) ? 1 : 0;
-    moff[i] = (uint64_t)(p - lb);
+    out->moff[i] = (uint64_t)(p - lb);
     if (!dense[i]) {
       if ((uint64_t)(end - p) < 9ull * cnt[i]) return GMX_ERR_FORMAT;
       uint32_t prev = 0;
@@ -761,26 +767,46 @@ extern "C" int gmx_match_import(gmx_match* mb, int stream, const void* long_buf,
       if (valid != cnt[i]) return GMX_ERR_FORMAT;  // the branch follows from the count
     }
     if (end - p < 2048) return GMX_ERR_FORMAT;
-    tail[i] = p;
+    out->tail[i] = p;
     p += 2048;
   }
   if (p != end) return GMX_ERR_FORMAT;
+  for (int i = 0; i < K; ++i, sb += 11) {
+    memcpy(&out->cms[i], sb, 8);
+    const uint8_t bp = sb[9];
+    if ((bp & (bp - 1)) != 0) return GMX_ERR_FORMAT;                    // bit_pos_: 0 or a power of two
+    if (out->cms[i] != 0 && out->cms[i] >= hs) return GMX_ERR_FORMAT;   // cur_match_ inside the history
+  }
+  return GMX_OK;
+}
+
+extern "C" int gmx_match_import(gmx_match* mb, int stream, const void* long_buf, size_t long_bytes,
+                                const void* short_buf, size_t short_bytes) {
+  if (!mb || stream < 0 || stream >= mb->S || !long_buf || !short_buf) return GMX_ERR_INVALID;
+  const GmxMatchDev& d = mb->dev;
+  const int K = d.k;
+  // ---- validate everything before the bank is touched
+  const uint8_t* const lb = (const uint8_t*)long_buf;
+  GmxMatchSection sec;
+  {
+    int rcv = match_validate_section(d, lb, long_bytes, (const uint8_t*)short_buf, short_bytes, &sec);
+    if (rcv) return rcv;
+  }
+  const uint64_t hs = sec.hs;
+  const uint8_t* const hist_src = sec.hist_src;
+  const uint32_t* const cnt = sec.cnt;
+  const uint8_t* const dense = sec.dense;
+  const uint64_t* const moff = sec.moff;
+  const uint8_t* const* const tail = sec.tail;
+  const uint64_t* const cms = sec.cms;
   GmxMatchModelState ms[GMX_MATCH_MAX_MODELS];
   GmxMatchStreamState ss;
-  const uint8_t* sp = (const uint8_t*)short_buf;
-  uint64_t cms[GMX_MATCH_MAX_MODELS] = {};
-  for (int i = 0; i < K; ++i, sp += 11) {
-    memcpy(&cms[i], sp, 8);
-    const uint8_t bp = sp[9];
-    if ((bp & (bp - 1)) != 0) return GMX_ERR_FORMAT;              // bit_pos_: 0 or a power of two
-    if (cms[i] != 0 && cms[i] >= hs) return GMX_ERR_FORMAT;        // cur_match_ inside the history
-  }
   // ---- the bank
   int rc = match_read_states(mb, stream, ms, &ss);  // (drains the bank's stream; keeps slot values and new_bit)
   if (rc) return rc;
   rc = match_ckpt_ready(mb);
   if (rc) return rc;
-  sp = (const uint8_t*)short_buf;
+  const uint8_t* sp = (const uint8_t*)short_buf;
   for (int i = 0; i < K; ++i, sp += 11) {
     ms[i].cur_match = (uint32_t)cms[i];
     ms[i].cur_byte = sp[8];
@@ -813,9 +839,9 @@ extern "C" int gmx_match_import(gmx_match* mb, int stream, const void* long_buf,
     a.model_off = mb->model_off_d;
     a.buf = staged;
     XCHK(hipMemcpyAsync(staged, lb, long_bytes, hipMemcpyHostToDevice, mb->stream));
-    XCHK(hipMemcpyAsync(mb->model_cnt_d, cnt, sizeof cnt, hipMemcpyHostToDevice, mb->stream));
-    XCHK(hipMemcpyAsync(mb->model_dense_d, dense, sizeof dense, hipMemcpyHostToDevice, mb->stream));
-    XCHK(hipMemcpyAsync(mb->model_off_d, moff, sizeof moff, hipMemcpyHostToDevice, mb->stream));
+    XCHK(hipMemcpyAsync(mb->model_cnt_d, cnt, sizeof sec.cnt, hipMemcpyHostToDevice, mb->stream));
+    XCHK(hipMemcpyAsync(mb->model_dense_d, dense, sizeof sec.dense, hipMemcpyHostToDevice, mb->stream));
+    XCHK(hipMemcpyAsync(mb->model_off_d, moff, sizeof sec.moff, hipMemcpyHostToDevice, mb->stream));
     XCHK(hipMemsetAsync(bank, 0, (size_t)d.tab_bytes, mb->stream));
     XCHK(gmx_launch_match_ckpt_scatter(&a, K, 256, mb->stream));
     if (hs)

@@ -1,6 +1,6 @@
-// gmx_models.h -- host-side C++ mirrors of the two feature models that live on the device next
+// gmx_models.h -- host-side C++ mirrors of the feature models that live on the device next
 // to the mixers: the reference's `Indirect` (models/indirect.{h,cpp}) and `LstmModel`
-// (models/lstm-model.{h,cpp}), over the C ABI of libgmxmix.so (include/gmxmix.h).  Header-only,
+// (models/lstm-model.{h,cpp}), and the owner of the `Match` models' bank, over the C ABI of libgmxmix.so (include/gmxmix.h).  Header-only,
 // C++17, no HIP types.  Same pattern as gmx_mixer.h: the objects keep their place in
 // Predictor::models_ and their Model signatures (model.h:22-37); what LongTermMemory owned for
 // them is owned by a bank object on the GPU.
@@ -12,6 +12,9 @@
 //                      active_models keeps the reference's order.  Learn likewise.
 //   gmx::Indirect      `Indirect(stm, bank, learning_rate, table_size, unsigned& context,
 //                      description, enable_analysis)` (indirect.h:16-18).
+//   gmx::MatchBank     stands where LongTermMemory::history and match_memory stood (long-term-memory.h:42-53, :82) for
+//                      the Match objects of n_streams Predictors = one gmx_match.  The owner only: construction and
+//                      checkpoints; the Match objects' Predict / Learn arrive with the model adapter.
 //   gmx::LstmBank      stands where LongTermMemory::neuron_layer_weights / lstm_output_layer stood
 //                      (long-term-memory.h:55-76); its constructor draws the initial weights from
 //                      rand() exactly like LstmLayer's (lstm-layer.cpp:179-194), so a Predictor that
@@ -202,6 +205,136 @@ inline void IndirectBank::PredictAll(const ShortTermMemory& stm) {
   for (size_t i = 0; i < models_.size(); ++i) contexts_[i] = models_[i]->context();  // read at call time
   Note(gmx_indirect_forward(h_, 0, contexts_.data(), stm.bit_context, pred_.data(), active_.data()));
 }
+
+// ---- Match -----------------------------------------------------------------------------------
+
+class MatchBank {
+ public:
+  explicit MatchBank(int device = 0) : device_(device) {}
+  ~MatchBank() {
+    if (h_) gmx_match_destroy(h_);
+  }
+  MatchBank(const MatchBank&) = delete;
+  MatchBank& operator=(const MatchBank&) = delete;
+
+  // One Match constructor call (match.h:19-21) in construction order; `slot` is what AddPrediction returned.  Before
+  // Finalize.  -> the model's index.
+  int Add(unsigned table_size, int limit, int slot) {
+    gmx_match_desc d;
+    d.table_size = table_size;
+    d.limit = limit;
+    d.slot = slot;
+    descs_.push_back(d);
+    return (int)descs_.size() - 1;
+  }
+  // Once, after the last Add.
+  int Finalize(uint64_t history_capacity, int n_streams = 1) {
+    if (h_) return GMX_OK;
+    status_ = gmx_match_create(&h_, descs_.data(), (int)descs_.size(), history_capacity, n_streams, device_);
+    return status_;
+  }
+  bool ready() const { return h_ != nullptr; }
+  int status() const { return status_; }
+  gmx_match* handle() { return h_; }
+  size_t size() const { return descs_.size(); }
+  int streams() const { return h_ ? gmx_match_n_streams(h_) : 0; }
+
+  // One stream through the per-stream calls: the history and match section of LongTermMemory::WriteToDisk /
+  // ReadFromDisk (long-term-memory.cpp:70-106, :162-190), same bytes, and Match::WriteToDisk / ReadFromDisk of the
+  // models in order (match.cpp:111-123, 11 bytes each) -- `.short` is read before `.long` (predictor.cpp:412-416), so
+  // ReadShortFromDisk keeps the bytes and ReadFromDisk completes the import.
+  void WriteToDisk(std::ofstream* s, int stream = 0) {
+    std::vector<char> l, sh;
+    if (Export(stream, &l, &sh)) s->write(l.data(), l.size());
+  }
+  void WriteShortToDisk(std::ofstream* s, int stream = 0) {
+    std::vector<char> l, sh;
+    if (Export(stream, &l, &sh)) s->write(sh.data(), sh.size());
+  }
+  void ReadShortFromDisk(std::ifstream* s) {
+    short_in_.resize(11 * descs_.size());
+    s->read(short_in_.data(), short_in_.size());
+  }
+  void ReadFromDisk(std::ifstream* s, int stream = 0) {
+    if (!h_) return;
+    std::vector<char> buf;
+    auto take = [&](size_t n) {
+      size_t at = buf.size();
+      buf.resize(at + n);
+      s->read(buf.data() + at, n);
+    };
+    take(8);
+    uint64_t hs;
+    memcpy(&hs, buf.data(), 8);
+    if (hs >= (1ull << 32)) {
+      Note(GMX_ERR_FORMAT);
+      return;
+    }
+    take((size_t)hs);
+    for (const gmx_match_desc& d : descs_) {
+      take(4);
+      uint32_t count;
+      memcpy(&count, buf.data() + buf.size() - 4, 4);
+      // (match.cpp's rule, in double: sparse records below 5/9 of the table)
+      take((double)count < (5.0 / 9.0) * (double)d.table_size ? (size_t)count * 9 : (size_t)d.table_size * 5);
+      take(2 * 256 * 4);
+    }
+    Note(gmx_match_import(h_, stream, buf.data(), buf.size(), short_in_.data(), short_in_.size()));
+  }
+  void Copy(const MatchBank* orig, int stream = 0, int orig_stream = 0) {  // long-term-memory.cpp:220-226 + Match::Copy
+    if (h_ && orig->h_) Note(gmx_match_copy(h_, stream, orig->h_, orig_stream));
+  }
+  // Checkpoint of every stream in one call (gmx_match_group_export / gmx_match_group_import): valid entries are found
+  // and packed on the device.  Stream i's long section -- the bytes WriteToDisk writes for it -- is
+  // long_buf[off[i] .. off[i + 1]), its short section short_buf[11 K i .. 11 K (i + 1)).  After Finalize.
+  int ExportAll(std::vector<char>* long_buf, std::vector<size_t>* off, std::vector<char>* short_buf) {
+    if (!h_) return GMX_ERR_STATE;
+    const int n = gmx_match_n_streams(h_);
+    off->assign((size_t)n + 1, 0);
+    int rc = gmx_match_group_export(h_, 0, n, nullptr, 0, off->data(), nullptr);
+    if (rc) return rc;
+    long_buf->resize(off->back() ? off->back() : 1);
+    short_buf->resize((size_t)n * 11 * descs_.size());
+    rc = gmx_match_group_export(h_, 0, n, long_buf->data(), long_buf->size(), off->data(), short_buf->data());
+    if (rc == GMX_OK) long_buf->resize(off->back());
+    return rc;
+  }
+  // GMX_ERR_FORMAT, and no bank touched, when any section is malformed.  Slot values and new_bit stay (they belong to
+  // ShortTermMemory's checkpoint: gmx_match_slots_set).
+  int ImportAll(const std::vector<char>& long_buf, const std::vector<size_t>& off, const std::vector<char>& short_buf) {
+    if (!h_) return GMX_ERR_STATE;
+    const int n = gmx_match_n_streams(h_);
+    if (off.size() != (size_t)n + 1 || off.back() > long_buf.size()) return GMX_ERR_INVALID;
+    if (short_buf.size() != (size_t)n * 11 * descs_.size()) return GMX_ERR_FORMAT;
+    return gmx_match_group_import(h_, 0, n, long_buf.data(), off.data(), short_buf.data());
+  }
+
+ private:
+  bool Note(int rc) {
+    if (rc != GMX_OK && status_ == GMX_OK) {
+      status_ = rc;
+      fprintf(stderr, "gmx::MatchBank: %s %s\n", gmx_strerror(rc), gmx_last_error());
+    }
+    return rc != GMX_OK;
+  }
+  bool Export(int stream, std::vector<char>* l, std::vector<char>* sh) {
+    if (!h_) return false;
+    size_t nl = 0, ns = 0;
+    if (Note(gmx_match_export(h_, stream, nullptr, &nl, nullptr, &ns))) return false;
+    l->resize(nl ? nl : 1);
+    sh->resize(ns ? ns : 1);
+    if (Note(gmx_match_export(h_, stream, l->data(), &nl, sh->data(), &ns))) return false;
+    l->resize(nl);
+    sh->resize(ns);
+    return true;
+  }
+
+  int device_;
+  gmx_match* h_ = nullptr;
+  int status_ = GMX_OK;
+  std::vector<gmx_match_desc> descs_;
+  std::vector<char> short_in_;
+};
 
 // ---- LSTM ------------------------------------------------------------------------------------
 

@@ -9,6 +9,9 @@ from . import _lib
 from ._lib import GmxError, MatchDesc, check
 
 
+CKPT_CHUNK = 16384  # GMX_MATCH_CKPT_CHUNK of csrc/gmx_match.h: entries a block of the checkpoint kernels walks
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -157,6 +160,32 @@ class MatchGroup:
         sb = np.frombuffer(short_bytes or b"\0", np.uint8)
         check(self.L.gmx_match_import(self.h, stream, _vp(lb), len(long_bytes), _vp(sb), len(short_bytes)),
               "gmx_match_import")
+
+    def export_all(self, first=0, count=None):
+        """(long_bytes, long_off, short_bytes) of streams [first, first + count) in one call (gmx_match_group_export):
+        stream first + i's long section is long_bytes[long_off[i]:long_off[i + 1]], its short section
+        short_bytes[11 K i:11 K (i + 1)] -- the bytes export(stream) gives."""
+        count = self.S - first if count is None else int(count)
+        off = (C.c_size_t * (max(count, 0) + 1))()
+        check(self.L.gmx_match_group_export(self.h, first, count, None, 0, off, None), "gmx_match_group_export(size)")
+        lb = np.zeros(max(1, off[count]), np.uint8)
+        sb = np.zeros(max(1, 11 * self.K * count), np.uint8)
+        check(self.L.gmx_match_group_export(self.h, first, count, _vp(lb), lb.size, off, _vp(sb)),
+              "gmx_match_group_export")
+        return lb[:off[count]].tobytes(), [int(o) for o in off], sb[:11 * self.K * count].tobytes()
+
+    def import_all(self, long_bytes, long_off, short_bytes, first=0):
+        """The inverse (gmx_match_group_import): section i goes to stream first + i.  A malformed section anywhere
+        raises GmxError (GMX_ERR_FORMAT) and leaves every bank as it was; slot values and new_bit stay."""
+        count = len(long_off) - 1
+        off = (C.c_size_t * (max(count, 0) + 1))(*[int(o) for o in long_off])
+        if count < 1 or off[count] > len(long_bytes):   # (the C call is not told the buffers' lengths)
+            raise GmxError(-1, "gmx_match_group_import")
+        if len(short_bytes) != 11 * self.K * count:
+            raise GmxError(-6, "gmx_match_group_import")
+        lb = np.frombuffer(long_bytes or b"\0", np.uint8)
+        sb = np.frombuffer(short_bytes or b"\0", np.uint8)
+        check(self.L.gmx_match_group_import(self.h, first, count, _vp(lb), off, _vp(sb)), "gmx_match_group_import")
 
     def copy_from(self, src, src_stream=0, dst_stream=0):
         check(self.L.gmx_match_copy(self.h, dst_stream, src.h, src_stream), "gmx_match_copy")

@@ -558,6 +558,22 @@ int gmx_match_import(gmx_match* mb, int stream, const void* long_buf, size_t lon
 int gmx_match_copy(gmx_match* dst, int dst_stream, gmx_match* src, int src_stream);
 int gmx_match_memory_usage(gmx_match* mb, int model, uint64_t* bytes);
 
+/* Checkpoint streams [first, first + count) of a Match bank in one call; valid entries are counted and packed on the
+ * device and every stream's section is assembled there.  Stream i's long section -- byte for byte what
+ * gmx_match_export gives for it -- lies at long_buf + long_off[i], long_off[i + 1] - long_off[i] bytes; its short
+ * section at short_buf + i * 11 * n_models.  long_off has count + 1 entries and is always filled.  long_buf == NULL
+ * and short_buf == NULL: sizes only (exactly one of them NULL: GMX_ERR_INVALID).  GMX_ERR_INVALID if long_cap <
+ * long_off[count]; nothing is written to long_buf or short_buf then.  count >= 1.  The sections are staged in one
+ * device buffer of long_off[count] bytes that lives for the call: GMX_ERR_NOMEM, and nothing written, if it cannot be
+ * had.  The number of launches, transfers and synchronisations of a call does not depend on count. */
+int gmx_match_group_export(gmx_match* mb, int first, int count, void* long_buf, size_t long_cap,
+                           size_t* long_off /* [count + 1] */, void* short_buf /* [count][11 * n_models] */);
+/* The inverse (long_off[0] need not be 0).  Every section is validated as gmx_match_import validates it BEFORE any
+ * bank is touched: a bad section anywhere (GMX_ERR_FORMAT) leaves all banks as they were.  Like gmx_match_import it
+ * leaves the slot values and new_bit alone, and drops a pending gmx_match_forward of the imported streams. */
+int gmx_match_group_import(gmx_match* mb, int first, int count, const void* long_buf,
+                           const size_t* long_off /* [count + 1] */, const void* short_buf);
+
 /* ==== Lock step through the whole device chain: S decoders, one device step per coded bit ======
  * The reference's Decoder (coder/decoder.cpp:19-39) learns each bit from Predict's own result, so S files being
  * restored on one GPU advance together, a bit per step (gmx_lockstep_* above does this for the mixers alone).  A
