@@ -3,7 +3,7 @@
 // Linked by dropin/Makefile against the reference's own translation units (feature models, coder,
 // runner-utils) with Predictor::AddMixers constructing gmx::GpuMixer -- the reference calls the product.
 //
-// usage: gmix_many [-d] [-T chunk_bits] [-n bytes] [--no-pin] [--cpus n] [--groups g] [--destroy] [--plain-exit] [--device d] <out dir> <input file>...
+// usage: gmix_many [-d] [-T chunk_bits] [-n bytes] [--no-pin] [--cpus n] [--groups g] [--match-history bytes] [--destroy] [--plain-exit] [--device d] <out dir> <input file>...
 //   each input is compressed to <out dir>/<index>.gmix exactly as `gmix -c` would (runner-utils.cpp:88-121);
 //   -n limits every input to its first n bytes (written to <out dir>/<index>.in first).
 //   -d: each input is a file `gmix -c` wrote and is restored to <out dir>/<index>.out as `gmix -d` would
@@ -111,6 +111,8 @@ int main(int argc, char** argv) {
       opt.device = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--groups") && a + 1 < argc)
       opt.groups = atoi(argv[++a]);
+    else if (!strcmp(argv[a], "--match-history") && a + 1 < argc)
+      opt.match_history = strtoull(argv[++a], 0, 0);  // (builds with gmx::GpuMatch: bytes of history per stream)
     else if (!strcmp(argv[a], "--plain-exit"))
       g_release_pages = false;  // (experiments: end as any process does)
     else if (!strcmp(argv[a], "--destroy"))
@@ -119,7 +121,7 @@ int main(int argc, char** argv) {
       break;
   }
   if (argc - a < 2) {
-    fprintf(stderr, "usage: %s [-d] [-T chunk_bits] [-n bytes] [--no-pin] [--cpus n] [--groups g] [--destroy] [--plain-exit] [--device d] <out dir> <input file>...\n", argv[0]);
+    fprintf(stderr, "usage: %s [-d] [-T chunk_bits] [-n bytes] [--no-pin] [--cpus n] [--groups g] [--match-history bytes] [--destroy] [--plain-exit] [--device d] <out dir> <input file>...\n", argv[0]);
     return 2;
   }
   const std::string out_dir = argv[a++];

@@ -566,6 +566,9 @@ extern "C" int gmx_match_slots_set(gmx_match* mb, int stream, const float* value
   if (rc) return rc;
   for (int i = 0; i < mb->dev.k; ++i) ms[i].slot_value = values[i];
   ss.new_bit = (uint32_t)new_bit;
+  // A new blackboard: the bit a pending forward predicted was perceived without being learned (the reference's
+  // generation loop, Perceive -> Predict with no Learn, tester.cpp:296-302), so the next forward is that bit's successor
+  mb->fwd_done[stream] = 0;
   return match_write_states(mb, stream, ms, &ss);
 }
 

@@ -74,6 +74,9 @@ struct BatchedOptions {
                                // the call returns -- for a command-line driver that exits next: 64 destructors give back
                                // 64 x 2 GB of address space page table by page table (1.8 s for 64 files), the kernel
                                // reclaims the same in one sweep at exit
+  uint64_t match_history = 0;  // BatchedCompressFiles / BatchedDecompressFiles, Predictors with gmx::GpuMatch: bytes of
+                               // history per stream (MixerPool::SetMatchHistoryCapacity); 0: $GMX_MATCH_HISTORY, else the
+                               // longest input (restoring: the longest output) + 1
   int max_cpus = -1;           // ... onto at most this many of them.  -1: twice what the container's CPU quota is worth
                                // (threads spread over every core of the node spend the quota in a burst and are then
                                // stopped together for the rest of each scheduler period, the device idle meanwhile; a
@@ -275,6 +278,7 @@ class BatchedCompressor : public RunAheadSink {
       p_->SetAnalysisFrequency(kNever);
       const int N = stm.num_predictions;
       const std::vector<int> ind_slots = bank_->IndirectSlots();
+      const std::vector<int> match_slots = bank_->MatchSlots();
       const int lstm_slot = bank_->LstmSlot();
       for (int i = 0; i < (int)stm.model_enable_analysis.size(); ++i) {
         if (!stm.model_enable_analysis[i]) continue;
@@ -289,6 +293,10 @@ class BatchedCompressor : public RunAheadSink {
         } else if (i == lstm_slot) {
           src.kind = kLstm;
           wants_models_ = true;
+        } else if (std::find(match_slots.begin(), match_slots.end(), i) != match_slots.end()) {
+          src.kind = kMatch;
+          src.index = (int)(std::find(match_slots.begin(), match_slots.end(), i) - match_slots.begin());
+          wants_models_ = true;
         } else {
           auto it = std::find(ind_slots.begin(), ind_slots.end(), i);
           if (it == ind_slots.end()) continue;  // a feature model on the host: the Predictor's own average is right
@@ -299,6 +307,14 @@ class BatchedCompressor : public RunAheadSink {
         src.ema = stm.entropy[i];
         on_device_.push_back(src);
       }
+    }
+    // The Match models on the device (gmx::GpuMatch): the bank's history has room for this input (a pool that was told
+    // its capacity keeps it), and analysis/memory.tsv's last column -- LongTermMemory::history.size(),
+    // predictor.cpp:500 -- is counted from the returned longest_match: the host's vector is not the history then.
+    has_match_ = bank_->HasMatch();
+    if (has_match_) {
+      bank_->WantMatchHistory(input_bytes + 1);
+      history_ = bank_->MatchHistorySize();
     }
     uint64_t chunk = opt_.chunk_bits < 8 ? 8 : opt_.chunk_bits & ~7ull;
     return bank_->BeginRunAhead(this, chunk);
@@ -380,16 +396,23 @@ class BatchedCompressor : public RunAheadSink {
             // (a model that stayed silent left the zero Predictor::Predict had put there, predictor.cpp:362-365)
             const size_t q = i * 2 * (size_t)v.n_ind + src.index;
             x = v.ind_active[q] ? v.ind_pred[q] : 0.0f;
+          } else if (src.kind == kMatch) {
+            const size_t q = i * (size_t)v.n_match + src.index;
+            x = v.match_active[q] ? v.match_pred[q] : 0.0f;
           } else {
             x = v.lstm_active[i] ? v.lstm_pred[i] : 0.0f;  // [byte][8] is bit order
           }
           src.ema = Average(src.ema, x, v.bits[i]);
         }
         if (!rows_.empty() && rows_.front().bit == drained_) {
+          if (has_match_) rows_.front().history = (size_t)history_;  // (RunAnalysis runs in Perceive: before this bit's Learn)
           WriteRow(rows_.front());
           rows_.pop_front();
         }
       }
+      // BasicContexts::Learn (basic-contexts.cpp:46-52): a completed byte joins the history unless longest_match >= 2
+      // (runs start on byte boundaries: Code / CodeByte code whole bytes)
+      if (has_match_ && v.match_longest && (drained_ & 7) == 7 && v.match_longest[i] < 2) ++history_;
       ++drained_;
     }
   }
@@ -455,7 +478,7 @@ class BatchedCompressor : public RunAheadSink {
   BatchedOptions opt_;
   std::shared_ptr<GpuMixerBank> bank_;
   int F_ = 0, sample_frequency_ = 0;
-  enum Kind { kMixer, kIndirect, kLstm };
+  enum Kind { kMixer, kIndirect, kLstm, kMatch };
   struct Source {   // an analysed entry whose values come from the device
     int column = 0;   // position in analysed_
     Kind kind = kMixer;
@@ -467,6 +490,8 @@ class BatchedCompressor : public RunAheadSink {
   bool wants_models_ = false, wants_all_outputs_ = false;
   std::deque<Row> rows_;
   uint64_t recorded_ = 0, drained_ = 0;
+  bool has_match_ = false;
+  uint64_t history_ = 0;  // LongTermMemory::history.size() as of the bits drained so far (Match models on the device)
 };
 
 // runner_utils::Compress (runner-utils.cpp:43-67), argument for argument; returns 0 or a gmx_status.
@@ -643,6 +668,16 @@ inline int BatchedCompressFiles(std::vector<BatchedJob>& jobs, const BatchedOpti
   const int S = (int)jobs.size();
   if (S == 0) return 0;
   MixerPool pool(S, opt.device);
+  {  // Predictors with gmx::GpuMatch: every stream's history has room for the longest input (nothing is restored here)
+    uint64_t longest = 0;
+    for (auto& j : jobs) {
+      std::error_code ec;
+      const auto n = std::filesystem::file_size(j.input_path, ec);
+      if (!ec) longest = std::max<uint64_t>(longest, n);
+    }
+    if (!opt.match_history && !getenv("GMX_MATCH_HISTORY")) pool.SetMatchHistoryCapacity(longest + 1);
+    if (opt.match_history) pool.SetMatchHistoryCapacity(opt.match_history);
+  }
   std::vector<std::ifstream> in(S);
   std::vector<std::ofstream> out(S);
   std::vector<std::unique_ptr<BatchedCompressor>> c(S);
@@ -883,6 +918,7 @@ inline int LockstepDecompress(unsigned long long output_length, std::ifstream* i
     fprintf(stderr, "gmx::LockstepDecompress: this Predictor's mixers are not gmx::GpuMixer\n");
     return GMX_ERR_INVALID;
   }
+  bank->WantMatchHistory(output_length + 1);
   int rc = bank->BeginLockstep();
   if (rc) return rc;
   {
@@ -921,9 +957,21 @@ inline int BatchedDecompressFiles(std::vector<BatchedJob>& jobs, const BatchedOp
   // file s belongs to pool s * G / S (whole stretches: the pools' streams are their files in order)
   std::vector<int> pool_of(S);
   std::vector<std::unique_ptr<MixerPool>> pools;
+  uint64_t match_history = opt.match_history;
+  if (!match_history && !getenv("GMX_MATCH_HISTORY")) {
+    // Predictors with gmx::GpuMatch: room for the longest OUTPUT (the length every coded file opens with)
+    for (auto& j : jobs) {
+      std::ifstream f(j.input_path, std::ios::in | std::ios::binary);
+      unsigned long long n = 0;
+      if (f.is_open()) runner_utils::ReadHeader(&f, &n);
+      if (f) match_history = std::max<uint64_t>(match_history, n);
+    }
+    ++match_history;
+  }
   for (int g = 0; g < G; ++g) {
     const int s0 = (int)((long long)S * g / G), s1 = (int)((long long)S * (g + 1) / G);
     pools.emplace_back(new MixerPool(s1 - s0, opt.device));
+    if (match_history) pools.back()->SetMatchHistoryCapacity(match_history);
     pools.back()->DrawLstmInit();  // (the draw IS rand(): here, before any constructor runs)
     for (int s = s0; s < s1; ++s) pool_of[s] = g;
   }
@@ -967,10 +1015,13 @@ inline int BatchedDecompressFiles(std::vector<BatchedJob>& jobs, const BatchedOp
   // fibre's last act is the wait for its last Learn.  (Runtime and profiler code on a 1 MB foreign stack: rocprofv3
   // around this very loop died with a segmentation fault while BeginLockstep still ran inside the fibres.)
   std::vector<std::shared_ptr<GpuMixerBank>> banks(S);
+  std::vector<char> ended(S, 0);  // the fibre ran to its end (a step that fails leaves the others where they wait)
   for (int s = 0; s < S; ++s) {
     runner.Add(s, pool_of[s], [&, s] {
       BatchedJob& job = jobs[s];
+      ended[s] = 1;
       if (job.status || !banks[s]) return;
+      ended[s] = 0;
       const clock::time_point a = clock::now();
       {
         Decoder d(&in[s], preds[s].get());  // runner_utils::Decompress (runner-utils.cpp:69-86), bit by bit
@@ -984,6 +1035,7 @@ inline int BatchedDecompressFiles(std::vector<BatchedJob>& jobs, const BatchedOp
       job.status = banks[s]->status();
       job.seconds = std::chrono::duration<double>(clock::now() - a).count();
       out[s].close();
+      ended[s] = 1;
     });
   }
   auto setup = [&](int w) {
@@ -1058,6 +1110,8 @@ inline int BatchedDecompressFiles(std::vector<BatchedJob>& jobs, const BatchedOp
       },
       [&](int g) { return pools[g]->StepWait(); });
   const clock::time_point t1 = clock::now();
+  for (int s = 0; s < S; ++s)  // a file whose pool failed under it (a step refused: the Match history's capacity) is not restored
+    if (!ended[s] && jobs[s].status == 0) jobs[s].status = pools[pool_of[s]]->status() ? pools[pool_of[s]]->status() : GMX_ERR_STATE;
   if (getenv("GMX_POOL_TRACE")) {
     auto sec = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     fprintf(stderr, "[gmx decode] %d files, %d workers, %d pool(s): pools %.2f s, Predictors (first alone: %.2f s) %.2f s, "
@@ -1066,6 +1120,8 @@ inline int BatchedDecompressFiles(std::vector<BatchedJob>& jobs, const BatchedOp
             sec(runner.join_done(), t0), (unsigned long long)steps, sec(t0, t1));
   }
   for (auto& p : pools) p->SetLockstepYield(nullptr);
+  for (auto& p : pools)  // (before the pools may be let go of below)
+    if (p->status() != 0) fprintf(stderr, "gmx::BatchedDecompressFiles: %s\n", p->error().c_str());
   if (opt.destroy_predictors) {
     // side by side, like their construction: a Predictor gives back gigabytes of touched pages, and one thread's munmap
     // after another's is all a process's exit would do about them either
@@ -1081,8 +1137,6 @@ inline int BatchedDecompressFiles(std::vector<BatchedJob>& jobs, const BatchedOp
   }
   int failed = 0;
   for (auto& j : jobs) failed += j.status != 0;
-  for (auto& p : pools)
-    if (p && p->status() != 0) fprintf(stderr, "gmx::BatchedDecompressFiles: %s\n", p->error().c_str());
   if (stats) {
     const clock::time_point tz = clock::now();
     stats->launches += steps;

@@ -64,6 +64,8 @@ class GpuMixerBank;
 class GpuIndirect;
 class GpuIndirectBank;
 class GpuLstmModel;
+class GpuMatch;
+class GpuMatchBank;
 
 // Process-wide tables of the adapters.  The reference lets several Predictors live in one process
 // (runner-utils.cpp:291-292); here they may also be built and run on different threads (one file per thread,
@@ -108,6 +110,11 @@ struct RunAheadView {
   const uint8_t* lstm_active = nullptr;
   const uint32_t* lstm_context = nullptr;  // [n / 8] ShortTermMemory::lstm_prediction_context of every byte (whenever the
                                            // LSTM is on the device: the blackboard keeps the newest)
+  // with the Match models on the device (gmx::GpuMatch), and only when asked for (RunAheadSink::WantsModels):
+  const float* match_pred = nullptr;       // [n][n_match] what the models' blackboard slots held
+  const uint8_t* match_active = nullptr;   // [n][n_match] whether SetPrediction marked them active
+  const uint32_t* match_longest = nullptr; // [n] ShortTermMemory::longest_match after the Match models' Predict
+  int n_match = 0;
 };
 struct RunAheadSink {
   virtual ~RunAheadSink() {}
@@ -121,8 +128,8 @@ struct RunAheadSink {
                                                            // bank then counts the rows it has seen on the host, bit by bit
 };
 
-// The device banks of up to n_streams Predictors -- ONE gmx_group, and one gmx_indirect / gmx_lstm where the
-// Predictors' Indirect models / LSTM are on the device as well -- one stream per Predictor, and the rings their
+// The device banks of up to n_streams Predictors -- ONE gmx_group, and one gmx_indirect / gmx_lstm / gmx_match where the
+// Predictors' Indirect models / LSTM / Match models are on the device as well -- one stream per Predictor, and the rings their
 // run-ahead chunks travel through.  Banks constructed while a pool is installed take a stream of it; otherwise
 // every Predictor owns a pool of one stream, which is the plain drop-in.  The Predictors may live on different
 // threads (one file per thread): every C-ABI call on the shared objects happens under the pool's mutex, the
@@ -144,8 +151,10 @@ class MixerPool {
       if (ring_[k]) gmx_batch_destroy(ring_[k]);
       if (iring_[k]) gmx_ind_batch_destroy(iring_[k]);
       if (lring_[k]) gmx_lstm_batch_destroy(lring_[k]);
+      if (mring_[k]) gmx_match_batch_destroy(mring_[k]);
     }
     if (cs_) gmx_chainstep_destroy(cs_);
+    if (match_) gmx_match_destroy(match_);
     if (group_) gmx_group_destroy(group_);
     if (ind_) gmx_indirect_destroy(ind_);
     if (lstm_) gmx_lstm_destroy(lstm_);
@@ -227,6 +236,16 @@ class MixerPool {
   gmx_group* group() const { return group_; }
   gmx_indirect* indirect() const { return ind_; }
   gmx_lstm* lstm() const { return lstm_; }
+  gmx_match* match() const { return match_; }
+  // Bytes of input history every stream's Match models can hold (gmx_match_create wants it up front): to be called
+  // before the first Predictor of the pool is used.  Without it: $GMX_MATCH_HISTORY, else kDefaultMatchHistory.  A run
+  // that would take a history past it ends with GMX_ERR_INVALID before anything is queued.
+  static constexpr uint64_t kDefaultMatchHistory = 1ull << 24;
+  void SetMatchHistoryCapacity(uint64_t bytes) {
+    std::lock_guard<std::mutex> lk(mu_);
+    match_cap_ = bytes < 1 ? 1 : bytes;
+  }
+  uint64_t match_history_capacity() const { return match_cap_; }
   // 0, or the status of the first C-ABI call that failed on this pool (shared pools report instead of aborting)
   int status() const { return status_.load(); }
   std::string error() const {
@@ -241,7 +260,7 @@ class MixerPool {
   double submit_seconds() const { return submit_seconds_; }
   double wait_seconds() const { return wait_seconds_; }
 
-  enum Parts { kMixers = 1, kIndirect = 2, kLstm = 4 };
+  enum Parts { kMixers = 1, kIndirect = 2, kLstm = 4, kMatch = 8 };
 
   // ---- lock step (decoding).  A decoder learns each bit from Predict's own result (coder/decoder.cpp:19-39), so
   // the Predictors of a pool that decode advance together, one device step (gmx_chainstep) per coded bit: every
@@ -291,6 +310,7 @@ class MixerPool {
   friend class GpuMixerBank;
   friend class GpuIndirectBank;
   friend class GpuLstmModel;
+  friend class GpuMatchBank;
 
   struct Stream {  // one Predictor's place in the pool
     const LongTermMemory* owner = nullptr;
@@ -298,6 +318,7 @@ class MixerPool {
     GpuMixerBank* mixers = nullptr;
     GpuIndirectBank* indirect = nullptr;
     GpuLstmModel* lstm = nullptr;
+    GpuMatchBank* match = nullptr;
     // run-ahead: where the chunk being filled is recorded, and how many bits of it are
     bool ra = false;
     uint64_t t = 0;
@@ -308,6 +329,10 @@ class MixerPool {
     uint8_t* ibits = nullptr;
     float* ppm = nullptr;
     uint8_t* bytes = nullptr;
+    uint32_t *mctx = nullptr, *mbc = nullptr;
+    uint8_t* mbits = nullptr;
+    uint8_t m_last_active[8] = {};  // the Match models' active flags of the newest bit that came back ...
+    bool m_last_valid = false;      // ... if one did (the sink asked for models)
     bool ls = false;  // lock step: Predict records into the chainstep's arrays and waits for the step
   };
 
@@ -420,13 +445,29 @@ class MixerPool {
     return gmx_indirect_create(&ind_, d.data(), (int)d.size(), ns, rm, S_, device_);
   }
   int EnsureLstm() { return lstm_ ? GMX_OK : gmx_lstm_create(&lstm_, S_, device_); }
+  int EnsureMatch(const std::vector<gmx_match_desc>& d) {
+    if (match_) {
+      bool same = d.size() == mdescs_.size();
+      for (size_t i = 0; same && i < d.size(); ++i)
+        same = d[i].table_size == mdescs_[i].table_size && d[i].limit == mdescs_[i].limit && d[i].slot == mdescs_[i].slot;
+      return same ? GMX_OK : GMX_ERR_INVALID;
+    }
+    if (!match_cap_) {
+      const char* e = getenv("GMX_MATCH_HISTORY");
+      const unsigned long long v = e ? strtoull(e, nullptr, 0) : 0;
+      match_cap_ = v ? v : kDefaultMatchHistory;
+    }
+    mdescs_ = d;
+    return gmx_match_create(&match_, d.data(), (int)d.size(), match_cap_, S_, device_);
+  }
 
   // ---- the ring ----
   // parts: which banks of the stream's Predictor are on the device (all streams of a pool alike);
   // lstm_slot / mixer_ctx_col / ind_ctx_col: where the LSTM's prediction and lstm_prediction_context go
   // (gmx_lstm_feed); models: the sink wants the feature models' predictions back as well
+  // match_cols: the gate-context columns that read ShortTermMemory::longest_match (gmx_match_run's ctx_columns)
   int Join(int slot, uint64_t chunk_bits, int parts, int lstm_slot, int mixer_ctx_col, int ind_ctx_col, bool models,
-           bool all_outputs) {
+           bool all_outputs, const std::vector<int32_t>& match_cols = std::vector<int32_t>()) {
     std::unique_lock<std::mutex> lk(mu_);
     if (status_.load()) return status_.load();
     if (!ring_[0]) {
@@ -435,6 +476,7 @@ class MixerPool {
       lstm_slot_ = lstm_slot;
       mixer_ctx_col_ = mixer_ctx_col;
       ind_ctx_col_ = ind_ctx_col;
+      match_cols_ = match_cols;
       models_back_ = models;
       all_outputs_ = all_outputs;
       for (int k = 0; k < kRing; ++k) {
@@ -461,16 +503,22 @@ class MixerPool {
           if (!gmx_lstm_batch_ppm(lring_[k]) || !gmx_lstm_batch_bytes(lring_[k]))
             return Fail("gmx_lstm_batch (pinned arrays)", GMX_ERR_NOMEM);
         }
+        if (parts_ & kMatch) {
+          if ((rc = gmx_match_batch_create(&mring_[k], match_, T_))) return Fail("gmx_match_batch_create", rc);
+          if (!gmx_match_batch_contexts(mring_[k]) || !gmx_match_batch_bit_contexts(mring_[k]) || !gmx_match_batch_bits(mring_[k]))
+            return Fail("gmx_match_batch (pinned arrays)", GMX_ERR_NOMEM);
+        }
       }
       n_pad_ = gmx_batch_n_pad(ring_[0]);
       mask_words_ = gmx_batch_mask_words(ring_[0]);
       M_ = gmx_group_n_mixers(group_);
       K_ = (parts_ & kIndirect) ? gmx_indirect_n_models(ind_) : 0;
+      KM_ = (parts_ & kMatch) ? gmx_match_n_models(match_) : 0;
       n_cur_.assign(S_, 0);
       for (int k = 0; k < kRing; ++k) n_in_[k].assign(S_, 0);
       n_bytes_.assign(S_, 0);
     } else if (parts != parts_ || lstm_slot != lstm_slot_ || mixer_ctx_col != mixer_ctx_col_ || ind_ctx_col != ind_ctx_col_ ||
-               (all_outputs && !all_outputs_)) {
+               match_cols != match_cols_ || (all_outputs && !all_outputs_)) {
       return GMX_ERR_INVALID;  // Predictors of different make in one pool (or a sink that needs what the ring does not carry)
     }
     models_back_ = models_back_ || models;
@@ -478,6 +526,7 @@ class MixerPool {
     for (int k = 0; k < kRing; ++k) n_in_[k][slot] = 0;
     streams_[slot].ra = true;
     streams_[slot].t = 0;
+    streams_[slot].m_last_valid = false;
     Records(slot);
     ++participants_;
     return GMX_OK;
@@ -498,6 +547,11 @@ class MixerPool {
     if (parts_ & kLstm) {
       st.ppm = gmx_lstm_batch_ppm(lring_[cur_]) + (size_t)slot * (T_ / 8) * 256;
       st.bytes = gmx_lstm_batch_bytes(lring_[cur_]) + (size_t)slot * (T_ / 8);
+    }
+    if (parts_ & kMatch) {
+      st.mctx = gmx_match_batch_contexts(mring_[cur_]) + (size_t)slot * T_ * KM_;
+      st.mbc = gmx_match_batch_bit_contexts(mring_[cur_]) + (size_t)slot * T_;
+      st.mbits = gmx_match_batch_bits(mring_[cur_]) + (size_t)slot * T_;
     }
   }
   // Every stream has handed in its chunk: queue it behind the chunk before, wait for THAT one.  mu_ held.
@@ -539,6 +593,8 @@ class MixerPool {
         GMX_POOL_STEP(gmx_lstm_batch_wait(lring_[other]));
         GMX_POOL_STEP(gmx_lstm_batch_download(lring_[other], on / 8));  // (44 bytes per byte: the context at least is wanted)
       }
+      // (the Match bank's transfers run on its own stream, behind the kernel that wrote the results)
+      if (models_back_ && (parts_ & kMatch)) GMX_POOL_STEP(gmx_match_batch_download(mring_[other], on));
     }
     const auto lead_tw = std::chrono::steady_clock::now();
     if (maxn > 0) {
@@ -550,6 +606,14 @@ class MixerPool {
       }
       if (parts_ & kIndirect) GMX_POOL_STEP(gmx_ind_batch_upload(iring_[c], maxn));
       GMX_POOL_STEP(gmx_batch_upload(ring_[c], maxn));
+      if (parts_ & kMatch) {
+        // Match::Predict / Learn x 6 of every bit of the chunk; predictions, active bits and longest_match (the gate
+        // context of the mixers that alias it) go into the mixers' records on the device.  Every writer of `into` waits
+        // for the upload above and for the writer before it, so any place between the upload and the mixers' run is
+        // right; this one is first because it waits for nothing else (gmx_lstm_feed stands behind the LSTM's kernels).
+        GMX_POOL_STEP(gmx_match_batch_upload(mring_[c], maxn));
+        GMX_POOL_STEP(gmx_match_run_ragged(match_, mring_[c], n_cur_.data(), ring_[c], match_cols_.data(), (int)match_cols_.size()));
+      }
       if (parts_ & kLstm) {
         GMX_POOL_STEP(gmx_lstm_feed(lstm_, lring_[c], maxn / 8, ring_[c], lstm_slot_, mixer_ctx_col_,
                                     (parts_ & kIndirect) && ind_ctx_col_ >= 0 ? iring_[c] : nullptr, ind_ctx_col_));
@@ -574,6 +638,7 @@ class MixerPool {
       GMX_POOL_STEP(gmx_batch_wait(ring_[other]));  // (the downloads queued at the top of this call)
       if (models_back_ && (parts_ & kIndirect)) GMX_POOL_STEP(gmx_ind_batch_wait(iring_[other]));
       if (parts_ & kLstm) GMX_POOL_STEP(gmx_lstm_batch_wait(lring_[other]));
+      if (models_back_ && (parts_ & kMatch)) GMX_POOL_STEP(gmx_match_batch_wait(mring_[other]));
     }
 #undef GMX_POOL_STEP
     if (rc) Fail(what, rc);
@@ -625,6 +690,16 @@ class MixerPool {
       v->lstm_active = gmx_lstm_batch_active(lring_[cur_]) + (size_t)slot * (T_ / 8) * 8;
       v->lstm_context = gmx_lstm_batch_contexts(lring_[cur_]) + (size_t)slot * (T_ / 8);
     }
+    if (models_back_ && (parts_ & kMatch)) {
+      v->match_pred = gmx_match_batch_predictions(mring_[cur_]) + (size_t)slot * T_ * KM_;
+      v->match_active = gmx_match_batch_active(mring_[cur_]) + (size_t)slot * T_ * KM_;
+      v->match_longest = gmx_match_batch_longest(mring_[cur_]) + (size_t)slot * T_;
+      v->n_match = KM_;
+      if (v->n && v->match_active) {
+        memcpy(streams_[slot].m_last_active, v->match_active + (size_t)(v->n - 1) * KM_, (size_t)KM_);
+        streams_[slot].m_last_valid = true;
+      }
+    }
     n_in_[cur_][slot] = 0;
     streams_[slot].t = 0;
     Records(slot);
@@ -643,7 +718,8 @@ class MixerPool {
   }
 
   // ---- lock step ----
-  int JoinLockstep(int slot, int parts, int lstm_slot, int mixer_ctx_col, int ind_ctx_col) {
+  int JoinLockstep(int slot, int parts, int lstm_slot, int mixer_ctx_col, int ind_ctx_col,
+                   const std::vector<int32_t>& match_cols = std::vector<int32_t>()) {
     std::unique_lock<std::mutex> lk(mu_);
     if (status_.load()) return status_.load();
     if (ring_[0]) return GMX_ERR_STATE;  // (a pool runs ahead or steps, not both)
@@ -651,16 +727,25 @@ class MixerPool {
       int rc = gmx_chainstep_create(&cs_, group_, (parts & kIndirect) ? ind_ : nullptr, (parts & kLstm) ? lstm_ : nullptr,
                                     lstm_slot, mixer_ctx_col, ind_ctx_col);
       if (rc) return Fail("gmx_chainstep_create", rc);
+      if (parts & kMatch) {  // once, before the object's first step
+        rc = gmx_chainstep_attach_match(cs_, match_, match_cols.data(), (int)match_cols.size());
+        if (rc) return Fail("gmx_chainstep_attach_match", rc);
+        if (!gmx_chainstep_match_contexts(cs_) || !gmx_chainstep_bit_contexts(cs_))
+          return Fail("gmx_chainstep (match records)", GMX_ERR_NOMEM);
+      }
+      match_cols_ = match_cols;
       parts_ = parts;
       lstm_slot_ = lstm_slot;
       mixer_ctx_col_ = mixer_ctx_col;
       ind_ctx_col_ = ind_ctx_col;
       M_ = gmx_group_n_mixers(group_);
       K_ = (parts_ & kIndirect) ? gmx_indirect_n_models(ind_) : 0;
+      KM_ = (parts_ & kMatch) ? gmx_match_n_models(match_) : 0;
       n_pad_ = (n_inputs_ + 3) / 4 * 4;
       mask_words_ = (n_inputs_ + 31) / 32;
       ls_what_ = gmx_chainstep_what(cs_);
-    } else if (parts != parts_ || lstm_slot != lstm_slot_ || mixer_ctx_col != mixer_ctx_col_ || ind_ctx_col != ind_ctx_col_) {
+    } else if (parts != parts_ || lstm_slot != lstm_slot_ || mixer_ctx_col != mixer_ctx_col_ || ind_ctx_col != ind_ctx_col_ ||
+               match_cols != match_cols_) {
       return GMX_ERR_INVALID;
     }
     streams_[slot].ls = true;
@@ -699,6 +784,10 @@ class MixerPool {
   gmx_group* group_ = nullptr;
   gmx_indirect* ind_ = nullptr;
   gmx_lstm* lstm_ = nullptr;
+  gmx_match* match_ = nullptr;
+  uint64_t match_cap_ = 0;  // 0: not set (EnsureMatch then takes the environment's or the default)
+  std::vector<gmx_match_desc> mdescs_;
+  std::vector<int32_t> match_cols_;
   int n_inputs_ = 0;
   std::vector<gmx_mixer_desc> descs_;
   std::vector<int32_t> skip_;
@@ -719,6 +808,7 @@ class MixerPool {
   gmx_batch* ring_[kRing] = {};
   gmx_ind_batch* iring_[kRing] = {};
   gmx_lstm_batch* lring_[kRing] = {};
+  gmx_match_batch* mring_[kRing] = {};
   bool busy_[kRing] = {};
   uint64_t maxn_[kRing] = {};   // bits of the longest stream of the chunk in each ring slot
   int cur_ = 0, parts_ = 0, lstm_slot_ = -1, mixer_ctx_col_ = -1, ind_ctx_col_ = -1;
@@ -728,7 +818,7 @@ class MixerPool {
   const bool trace_ = getenv("GMX_POOL_TRACE") != nullptr;
   std::map<std::string, double> step_seconds_;
   std::vector<std::chrono::steady_clock::time_point> left_at_;  // (trace) when each stream last left Arrive
-  int n_pad_ = 0, mask_words_ = 0, M_ = 0, K_ = 0;
+  int n_pad_ = 0, mask_words_ = 0, M_ = 0, K_ = 0, KM_ = 0;
   int participants_ = 0, arrived_ = 0;
   std::vector<uint64_t> n_cur_, n_in_[kRing], n_bytes_;
 };
@@ -785,6 +875,24 @@ class GpuMixerBank {
   // prediction slots of Indirect model i ([2i] indirect, [2i+1] run map), the LSTM's slot (-1: on the host)
   std::vector<int> IndirectSlots() const;
   int LstmSlot() const;
+  // whether this Predictor's Match models are gmx::GpuMatch, and LongTermMemory::history.size() as the bank has it
+  bool HasMatch() const { return pool_->streams_[slot_].match != nullptr; }
+  uint64_t MatchHistorySize();
+  std::vector<int> MatchSlots() const;
+  // A driver that knows how long the stream gets: the capacity of a pool whose Match bank does not stand yet and that
+  // was told nothing (MixerPool::SetMatchHistoryCapacity, $GMX_MATCH_HISTORY).  A history grows by at most a byte per
+  // byte coded.
+  void WantMatchHistory(uint64_t bytes) {
+    if (!HasMatch() || pool_->match() || pool_->match_history_capacity() || getenv("GMX_MATCH_HISTORY")) return;
+    pool_->SetMatchHistoryCapacity(bytes);
+  }
+  // the gate-context columns whose mixers alias ShortTermMemory::longest_match (found by address; 6 and 30 for the stock Predictor)
+  std::vector<int32_t> MatchColumns() const {
+    std::vector<int32_t> v;
+    for (size_t j = 0; j < mixers_.size(); ++j)
+      if (MixerContextAddress(j) == &stm_.longest_match) v.push_back((int32_t)j);
+    return v;
+  }
   int SlotsHome();  // the device-side models' prediction slots, back onto the blackboard
 
   // From the next Predict on, the device-side models record instead of compute; results reach `sink` one chunk
@@ -820,6 +928,8 @@ class GpuMixerBank {
   friend class GpuMixer;
   friend class GpuIndirectBank;
   friend class GpuLstmModel;
+  friend class GpuMatchBank;
+  const unsigned int* MixerContextAddress(size_t j) const;
   GpuMixerBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
     pool_ = MixerPool::Attach(&ltm, &slot_);
     std::lock_guard<std::mutex> lk(pool_->mu_);
@@ -980,6 +1090,7 @@ class GpuMixerBank {
         const uint32_t* c = s.ctx + (size_t)s.t * descs_.size();
         for (size_t j = 0; j < descs_.size(); ++j) {
           if ((int)j == lstm_ctx_col_) continue;    // (that context is the device's: counted when its chunk returns)
+          if (std::find(match_cols_.begin(), match_cols_.end(), (int32_t)j) != match_cols_.end()) continue;  // (likewise)
           if (!first_mark_ && c[j] == last_ctx_[j]) continue;  // (most contexts stand for a whole byte)
           last_ctx_[j] = c[j];
           MarkSeen(j, c[j]);
@@ -1060,6 +1171,7 @@ class GpuMixerBank {
   RunAheadSink* sink_ = nullptr;
   uint64_t T_ = 0;
   int n_pad_ = 0, mask_words_ = 0, lstm_ctx_col_ = -1;
+  std::vector<int32_t> match_cols_;  // gate-context columns the device fills with longest_match (run-ahead)
   std::vector<std::vector<uint64_t>> seen_;
   std::vector<uint32_t> last_ctx_;   // the context each mixer's row was last marked for
   std::vector<uint8_t> last_ind_active_;  // the Indirect models' active flags of the newest bit that came back
@@ -1705,7 +1817,381 @@ class GpuLstmModel : public Model {
   bool range_on_device_ = false;  // top_/mid_/bot_/probs_ were last advanced by the device (run-ahead)
 };
 
+// ================================================================================================
+// `gmx::GpuMatch` with Match's constructor signature (models/match.h:19-21): the six Match models of the reference's
+// Predictor (predictor.cpp:187-208) as one stream of a gmx_match bank, switched in like the others (`new Match(` ->
+// `new gmx::GpuMatch(` at its 6 places; dropin/Makefile builds gmix_full / ref_tester_full that way).  The bank owns
+// the deduplicated input history and the pointer tables: LongTermMemory::history and ::match_memory[..].table are only
+// the staging area of the reference's serialisers (as ::mixers and ::indirect are for the other banks) -- filled from
+// the device before LongTermMemory::WriteToDisk, imported after ReadFromDisk; the tables are empty otherwise.  The
+// host's BasicContexts::Learn still pushes bytes into LongTermMemory::history.  Per bit it sees the longest_match the
+// bank's forward stored, so the vector goes on mirroring the device's history and Predictor::RunAnalysis reads the
+// right size from it (predictor.cpp:500).  While the device runs ahead or in lock step the host's longest_match stays 0
+// and every byte would be pushed: the bank empties the vector at every Learn (nothing on the host reads it then --
+// gmx_batched.h takes the analysis column from the returned longest_match) and gives it the device's size again,
+// not its bytes, when the stream comes home.
+// ================================================================================================
+class GpuMatchBank {
+ public:
+  static std::shared_ptr<GpuMatchBank> For(ShortTermMemory& stm, LongTermMemory& ltm) {
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    auto& reg = Registry();
+    auto it = reg.find(&ltm);
+    if (it != reg.end())
+      if (auto sp = it->second.lock()) return sp;
+    std::shared_ptr<GpuMatchBank> sp(new GpuMatchBank(stm, ltm));
+    reg[&ltm] = sp;
+    return sp;
+  }
+  ~GpuMatchBank() {
+    {
+      std::lock_guard<std::mutex> lk(pool_->mu_);
+      st().match = nullptr;
+    }
+    pool_->Detach(slot_);
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    Registry().erase(&ltm_);
+  }
+  GpuMatchBank(const GpuMatchBank&) = delete;
+  GpuMatchBank& operator=(const GpuMatchBank&) = delete;
+
+ private:
+  friend class GpuMatch;
+  friend class GpuMixerBank;
+  GpuMatchBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
+    pool_ = MixerPool::Attach(&ltm, &slot_);
+    std::lock_guard<std::mutex> lk(pool_->mu_);
+    st().match = this;
+  }
+  static std::map<const LongTermMemory*, std::weak_ptr<GpuMatchBank>>& Registry() {
+    static std::map<const LongTermMemory*, std::weak_ptr<GpuMatchBank>> r;
+    return r;
+  }
+  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
+  template <class F>
+  void Call(const char* what, F f) {
+    pool_->Call("gmx::GpuMatch", what, f);
+  }
+  int Register(GpuMatch* m, unsigned table_size, int limit, int slot, int memory_index) {
+    gmx_match_desc d;
+    d.table_size = table_size;
+    d.limit = limit;
+    d.slot = slot;
+    descs_.push_back(d);
+    models_.push_back(m);
+    memory_index_.push_back(memory_index);
+    return (int)descs_.size() - 1;
+  }
+  void Ensure() {
+    if (h_) return;
+    Call("gmx_match_create", [&] { return pool_->EnsureMatch(descs_); });
+    h_ = pool_->match();
+    contexts_.assign(descs_.size(), 0u);
+    pred_.assign(descs_.size(), 0.f);
+    slots_ = pred_;
+    active_.assign(descs_.size(), 0);
+    short_cache_.assign(11 * descs_.size(), 0);
+    for (size_t i = 0; i < descs_.size(); ++i) short_cache_[11 * i + 9] = (char)128;  // a fresh Match: bit_pos_ 128
+    short_in_ = short_cache_;
+  }
+  // The pointer tables (5 bytes per entry, 115 MB for the stock models) exist on the host only around the reference's
+  // serialisers: sized before LongTermMemory::ReadFromDisk, which writes into them, and while staged for WriteToDisk.
+  void HostTables(bool on) {
+    for (size_t i = 0; i < descs_.size(); ++i) {
+      auto& table = ltm_.match_memory[memory_index_[i]].table;
+      if (on)
+        table.assign(descs_[i].table_size, std::array<unsigned char, 5>{{0, 0, 0, 0, 0}});
+      else
+        std::vector<std::array<unsigned char, 5>>().swap(table);
+    }
+  }
+  // The mixers' bank brings every chunk in flight home (the Match models' Copy / WriteToDisk come before the mixers').
+  void SyncIfAhead();
+  // What LongTermMemory::ReadFromDisk has read since ReadFromDisk was called on the models goes to the device, in the
+  // section's own format (long-term-memory.cpp:70-106); the blackboard's slots and new_bit follow (they are
+  // ShortTermMemory's, restored by then).
+  void Settle() {
+    Ensure();
+    if (!import_pending_) return;
+    SyncIfAhead();
+    import_pending_ = false;
+    std::vector<char> buf;
+    auto put = [&buf](const void* p, size_t n) {
+      const char* c = static_cast<const char*>(p);
+      buf.insert(buf.end(), c, c + n);
+    };
+    const unsigned long long hs = ltm_.history.size();
+    put(&hs, 8);
+    put(ltm_.history.data(), ltm_.history.size());
+    for (size_t i = 0; i < descs_.size(); ++i) {
+      auto& mem = ltm_.match_memory[memory_index_[i]];
+      std::vector<unsigned int> keys;
+      for (unsigned int k = 0; k < mem.table.size(); ++k) {
+        const auto& e = mem.table[k];
+        if (e[0] || e[1] || e[2] || e[3] || e[4]) keys.push_back(k);
+      }
+      unsigned int size = (unsigned int)keys.size();
+      put(&size, 4);
+      if (size < (5.0 / 9.0) * mem.table.size()) {
+        for (unsigned int key : keys) {
+          put(&key, 4);
+          put(mem.table[key].data(), 5);
+        }
+      } else {
+        put(mem.table.data(), 5 * mem.table.size());
+      }
+      put(mem.predictions.data(), 256 * 4);
+      put(mem.counts.data(), 256 * 4);
+    }
+    Call("gmx_match_import", [&] {
+      return gmx_match_import(h_, slot_, buf.data(), buf.size(), short_in_.data(), short_in_.size());
+    });
+    HostTables(false);
+    staged_ = false;
+    SlotsToDevice(stm_);  // (the import, and this, drop a pending forward)
+  }
+  // Device -> LongTermMemory::history / ::match_memory (+ the 11 bytes of every model), for the reference's writers.
+  void Stage() {
+    Settle();
+    SyncIfAhead();
+    size_t nl = 0, ns = 0;
+    Call("gmx_match_export", [&] { return gmx_match_export(h_, slot_, nullptr, &nl, nullptr, &ns); });
+    std::vector<char> l(nl ? nl : 1);
+    short_cache_.assign(ns ? ns : 1, 0);
+    Call("gmx_match_export", [&] { return gmx_match_export(h_, slot_, l.data(), &nl, short_cache_.data(), &ns); });
+    if (pool_->status()) return;
+    short_cache_.resize(ns);
+    HostTables(true);
+    const char* p = l.data();
+    unsigned long long hs;
+    memcpy(&hs, p, 8);
+    p += 8;
+    ltm_.history.assign(reinterpret_cast<const unsigned char*>(p), reinterpret_cast<const unsigned char*>(p) + hs);
+    p += hs;
+    for (size_t i = 0; i < descs_.size(); ++i) {
+      auto& mem = ltm_.match_memory[memory_index_[i]];
+      unsigned int count;
+      memcpy(&count, p, 4);
+      p += 4;
+      if (count < (5.0 / 9.0) * mem.table.size()) {
+        for (unsigned int k = 0; k < count; ++k) {
+          unsigned int key;
+          memcpy(&key, p, 4);
+          memcpy(mem.table[key].data(), p + 4, 5);
+          p += 9;
+        }
+      } else {
+        memcpy(mem.table.data(), p, 5 * mem.table.size());
+        p += 5 * mem.table.size();
+      }
+      memcpy(mem.predictions.data(), p, 1024);
+      memcpy(mem.counts.data(), p + 1024, 1024);
+      p += 2048;
+    }
+    staged_ = true;
+  }
+  void Unstage() {
+    if (staged_ && !import_pending_) {
+      HostTables(false);
+      staged_ = false;
+    }
+  }
+  void SlotsToDevice(const ShortTermMemory& stm) {
+    for (size_t i = 0; i < descs_.size(); ++i) pred_[i] = stm.predictions[descs_[i].slot];
+    Call("gmx_match_slots_set", [&] { return gmx_match_slots_set(h_, slot_, pred_.data(), stm.new_bit ? 1 : 0); });
+    fwd_pending_ = false;
+  }
+  // The models' slots, and longest_match as the newest bit's six Predicts left it: max(match_length_ / 32)
+  // (match.cpp:70-73 after basic-contexts.cpp:39; Learn does not move match_length_) from the models' short section.
+  void HomeFromDevice(ShortTermMemory& stm, bool silent_are_zero) {
+    Call("gmx_match_slots_get", [&] { return gmx_match_slots_get(h_, slot_, pred_.data(), nullptr); });
+    size_t nl = 0, ns = short_cache_.size();
+    std::vector<char> sh(ns);
+    Call("gmx_match_export", [&] { return gmx_match_export(h_, slot_, nullptr, &nl, sh.data(), &ns); });
+    if (pool_->status()) return;
+    unsigned int longest = 0;
+    for (size_t i = 0; i < descs_.size(); ++i) {
+      stm.predictions[descs_[i].slot] = pred_[i];
+      if (silent_are_zero && st().m_last_valid && !st().m_last_active[i]) stm.predictions[descs_[i].slot] = 0;
+      longest = std::max(longest, (unsigned int)(unsigned char)sh[11 * i + 10] / 32u);
+    }
+    stm.longest_match = longest;
+    uint64_t hs = 0;  // the vector's size is the device's again (its bytes are staged when a serialiser wants them)
+    Call("gmx_match_history_size", [&] { return gmx_match_history_size(h_, slot_, &hs); });
+    if (pool_->status() == 0 && ltm_.history.size() != hs) ltm_.history.assign((size_t)hs, 0);
+  }
+  uint64_t HistorySize() {
+    Settle();
+    SyncIfAhead();
+    uint64_t v = 0;
+    Call("gmx_match_history_size", [&] { return gmx_match_history_size(h_, slot_, &v); });
+    return v;
+  }
+  void PredictAll(ShortTermMemory& stm);
+  void LearnAll(const ShortTermMemory& stm) {
+    Settle();
+    Unstage();
+    MixerPool::Stream& s = st();
+    if (s.ls || s.ra) ltm_.history.clear();  // (what BasicContexts::Learn has just pushed: the bank keeps the history)
+    if (s.ls) return;  // (lock step: the mixers' Learn asks for the step's learn, which is every device-side model's)
+    if (s.ra) {
+      s.mbits[s.t] = (uint8_t)stm.new_bit;  // the history push of BasicContexts::Learn + Match::Learn x 6, recorded
+      return;
+    }
+    if (!fwd_pending_) return;  // (a Learn without its Predict: nothing was predicted to learn from)
+    fwd_pending_ = false;
+    Call("gmx_match_learn", [&] { return gmx_match_learn(h_, slot_, stm.new_bit ? 1 : 0); });
+  }
+  void CopyFrom(GpuMatchBank& o) {
+    o.Settle();
+    o.SyncIfAhead();
+    o.Unstage();  // (LongTermMemory::Copy, which follows, would copy the staged history and tables)
+    Ensure();
+    SyncIfAhead();
+    import_pending_ = false;
+    Unstage();
+    if (o.pool_ == pool_) {
+      Call("gmx_match_copy", [&] { return gmx_match_copy(h_, slot_, o.h_, o.slot_); });
+    } else {  // two banks: both pools' calls held off, always in address order
+      MixerPool* a = pool_.get() < o.pool_.get() ? pool_.get() : o.pool_.get();
+      MixerPool* b = pool_.get() < o.pool_.get() ? o.pool_.get() : pool_.get();
+      int rc;
+      {
+        std::lock_guard<std::mutex> la(a->mu_);
+        std::lock_guard<std::mutex> lb(b->mu_);
+        rc = gmx_match_copy(h_, slot_, o.h_, o.slot_);
+      }
+      pool_->Check("gmx::GpuMatch", "gmx_match_copy", rc);
+    }
+    fwd_pending_ = false;  // (gmx_match_copy drops it)
+  }
+
+  ShortTermMemory& stm_;
+  LongTermMemory& ltm_;
+  std::shared_ptr<MixerPool> pool_;
+  int slot_ = 0;
+  gmx_match* h_ = nullptr;
+  std::vector<gmx_match_desc> descs_;
+  std::vector<GpuMatch*> models_;
+  std::vector<int> memory_index_;
+  std::vector<uint32_t> contexts_;
+  std::vector<float> pred_;
+  std::vector<uint8_t> active_;
+  std::vector<char> short_cache_, short_in_;
+  bool import_pending_ = false, staged_ = false;
+  bool fwd_pending_ = false;  // per bit: a gmx_match_forward waits for its learn
+  std::vector<float> slots_;  // ... and the slot values it reported
+  bool ls_fresh_ = false;  // lock step: the stream's first Predict through the chainstep object is still to come
+};
+
+class GpuMatch : public Model {
+ public:
+  // models/match.h:19-21, argument for argument.
+  GpuMatch(ShortTermMemory& short_term_memory, LongTermMemory& long_term_memory, unsigned int table_size,
+           const unsigned int& byte_context, int limit, std::string description, bool enable_analysis)
+      : byte_context_(byte_context), bank_(GpuMatchBank::For(short_term_memory, long_term_memory)) {
+    // match.cpp:14-22: the registrations Match::Match makes.  The table in LongTermMemory is only the staging area of
+    // the reference's serialisers here and stays empty until one runs (GpuMatchBank::HostTables).
+    const int slot = short_term_memory.AddPrediction(description, enable_analysis, this);
+    const int memory_index = (int)long_term_memory.match_memory.size();
+    long_term_memory.match_memory.push_back(MatchMemory(0));
+    auto& memory = long_term_memory.match_memory.back();
+    for (int i = 0; i < 256; ++i) memory.predictions[i] = 0.5 + (i + 0.5) / 512;
+    memory.counts.fill(1);
+    index_ = bank_->Register(this, table_size, limit, slot, memory_index);
+  }
+  // The bank runs when the LAST Match model is called (the rule of gmx::GpuIndirect): every context is final by then and
+  // nothing between the Match models reads their predictions or longest_match.
+  void Predict(ShortTermMemory& short_term_memory, const LongTermMemory&) override {
+    if (index_ + 1 == (int)bank_->models_.size()) bank_->PredictAll(short_term_memory);
+  }
+  // (after BasicContexts::Learn, the first model of the Predictor: its history push is the bank's own, basic-contexts.cpp:44-53)
+  void Learn(const ShortTermMemory& short_term_memory, LongTermMemory&) override {
+    if (index_ == 0) bank_->LearnAll(short_term_memory);
+  }
+  void WriteToDisk(std::ofstream* s) override {  // match.cpp:111-116: 11 bytes; the bank staged for the .long writer
+    if (index_ == 0) bank_->Stage();
+    s->write(&bank_->short_cache_[11 * (size_t)index_], 11);
+  }
+  void ReadFromDisk(std::ifstream* s) override {  // match.cpp:118-123; the reference reads history and tables next
+    bank_->Ensure();
+    s->read(&bank_->short_in_[11 * (size_t)index_], 11);
+    bank_->import_pending_ = true;
+    if (index_ == 0) bank_->HostTables(true);
+  }
+  void Copy(const MemoryInterface* m) override {  // match.cpp:125-131 + LongTermMemory::Copy's share
+    const GpuMatch* orig = static_cast<const GpuMatch*>(m);
+    if (index_ == 0) bank_->CopyFrom(*orig->bank_);
+  }
+  unsigned long long GetMemoryUsage(const ShortTermMemory&, const LongTermMemory&) override {  // match.cpp:133-141
+    bank_->Ensure();
+    uint64_t v = 0;
+    bank_->Call("gmx_match_memory_usage", [&] { return gmx_match_memory_usage(bank_->h_, index_, &v); });
+    return v;
+  }
+  unsigned int context() const { return byte_context_; }
+
+ private:
+  const unsigned int& byte_context_;  // aliases a field of the Predictor's blackboard (match.h:33)
+  std::shared_ptr<GpuMatchBank> bank_;
+  int index_;
+};
+
+inline void GpuMatchBank::PredictAll(ShortTermMemory& stm) {
+  Settle();
+  Unstage();
+  if (pool_->status()) return;
+  MixerPool::Stream& s = st();
+  if (s.ls) {
+    // lock step: bit_context on every predict; the contexts when a byte opens and on the stream's first predict
+    // through the object (gmx_chainstep_attach_match).  The mixers' Predict, last in line, waits for the step.
+    gmx_chainstep_bit_contexts(pool_->cs_)[slot_] = stm.bit_context;
+    if (ls_fresh_ || stm.bit_context == 0) {
+      uint32_t* c = gmx_chainstep_match_contexts(pool_->cs_) + (size_t)slot_ * models_.size();
+      for (size_t i = 0; i < models_.size(); ++i) c[i] = models_[i]->context();
+      ls_fresh_ = false;
+    }
+    return;
+  }
+  if (s.ra) {  // Match::Predict x 6, recorded
+    uint32_t* c = s.mctx + (size_t)s.t * models_.size();
+    for (size_t i = 0; i < models_.size(); ++i) c[i] = models_[i]->context();
+    s.mbc[s.t] = stm.bit_context;
+    return;
+  }
+  for (size_t i = 0; i < models_.size(); ++i) contexts_[i] = models_[i]->context();
+  if (fwd_pending_) {
+    // Predict -> Perceive -> Predict with no Learn in between (generation, tester.cpp:296-302): Match::Predict compares
+    // the perceived bit with the history all the same (match.cpp:29).  The bank gets it as new_bit, with the slot values
+    // it reported last, and takes the next forward as that bit's successor (gmx_match_slots_set).
+    Call("gmx_match_slots_set", [&] { return gmx_match_slots_set(h_, slot_, slots_.data(), stm.new_bit ? 1 : 0); });
+  }
+  uint32_t longest = 0;
+  Call("gmx_match_forward", [&] {
+    return gmx_match_forward(h_, slot_, contexts_.data(), stm.bit_context, pred_.data(), active_.data(), &longest);
+  });
+  if (pool_->status()) return;
+  fwd_pending_ = true;
+  slots_ = pred_;
+  // What 6 x Match::Predict leave on the blackboard (match.cpp:60-73 through SetPrediction,
+  // short-term-memory.cpp:187-191): an active model stores its logit and joins active_models; p == 0.5 stores a zero
+  // logit without becoming active; a silent model stores nothing -- the bank then reports the slot's old value.
+  for (size_t i = 0; i < descs_.size(); ++i) {
+    if (active_[i]) {
+      stm.predictions[descs_[i].slot] = pred_[i];
+      stm.active_models.push_back(descs_[i].slot);
+    } else if (pred_[i] == 0) {
+      stm.predictions[descs_[i].slot] = 0;
+    }
+  }
+  stm.longest_match = std::max(stm.longest_match, (unsigned int)longest);
+}
+
 // ---- the parts of the mixers' bank that know the other two ---------------------------------------------------
+inline void GpuMatchBank::SyncIfAhead() {
+  MixerPool::Stream& s = st();
+  if (s.ra && s.mixers) s.mixers->SyncRunAhead();
+}
 inline void GpuLstmModel::SyncIfAhead() {
   MixerPool::Stream& s = st();
   if (s.ra && s.mixers) s.mixers->SyncRunAhead();
@@ -1720,6 +2206,18 @@ inline std::vector<int> GpuMixerBank::IndirectSlots() const {
       v.push_back(d.slot_run_map);
     }
   return v;
+}
+inline const unsigned int* GpuMixerBank::MixerContextAddress(size_t j) const { return mixers_[j]->context_address(); }
+inline std::vector<int> GpuMixerBank::MatchSlots() const {
+  std::vector<int> v;
+  const GpuMatchBank* mb = pool_->streams_[slot_].match;
+  if (mb)
+    for (auto& d : mb->descs_) v.push_back(d.slot);
+  return v;
+}
+inline uint64_t GpuMixerBank::MatchHistorySize() {
+  GpuMatchBank* mb = st().match;
+  return mb ? mb->HistorySize() : 0;
 }
 inline int GpuMixerBank::LstmSlot() const {
   const GpuLstmModel* l = pool_->streams_[slot_].lstm;
@@ -1752,7 +2250,15 @@ inline int GpuMixerBank::BeginRunAhead(RunAheadSink* sink, uint64_t chunk_bits) 
       for (size_t i = 0; i < s.indirect->models_.size(); ++i)
         if (s.indirect->models_[i]->context_address() == &stm_.lstm_prediction_context) ind_ctx_col = (int)i;
   }
+  std::vector<int32_t> match_cols;
+  if (s.match) {
+    s.match->Settle();
+    s.match->SlotsToDevice(stm_);
+    parts |= MixerPool::kMatch;
+    match_cols = MatchColumns();
+  }
   if (status()) return status();
+  match_cols_ = match_cols;
   lstm_ctx_col_ = mixer_ctx_col;
   // rows this bank has seen (Mixer::contexts_seen_ / GetMemoryUsage while the device runs behind), when the sink
   // will ask: 33 modulos and bitmap words per bit otherwise spent for nothing
@@ -1775,7 +2281,7 @@ inline int GpuMixerBank::BeginRunAhead(RunAheadSink* sink, uint64_t chunk_bits) 
     Unstage();
   }
   int rc = pool_->Join(slot_, chunk_bits, parts, lstm_slot, mixer_ctx_col, ind_ctx_col, sink && sink->WantsModels(),
-                       sink && sink->WantsAllOutputs());
+                       sink && sink->WantsAllOutputs(), match_cols);
   if (rc) return rc;
   T_ = pool_->chunk_bits();
   n_pad_ = pool_->n_pad_;
@@ -1808,10 +2314,18 @@ inline int GpuMixerBank::BeginLockstep() {
       for (size_t i = 0; i < s.indirect->models_.size(); ++i)
         if (s.indirect->models_[i]->context_address() == &stm_.lstm_prediction_context) ind_ctx_col = (int)i;
   }
+  std::vector<int32_t> match_cols;
+  if (s.match) {
+    s.match->Settle();
+    s.match->SlotsToDevice(stm_);
+    s.match->ls_fresh_ = true;
+    parts |= MixerPool::kMatch;
+    match_cols = MatchColumns();
+  }
   if (status()) return status();
   ls_predicted_ = false;
   ever_ran_ = true;
-  return pool_->JoinLockstep(slot_, parts, lstm_slot, mixer_ctx_col, ind_ctx_col);
+  return pool_->JoinLockstep(slot_, parts, lstm_slot, mixer_ctx_col, ind_ctx_col, match_cols);
 }
 
 inline void GpuMixerBank::FinishLockstep() {
@@ -1827,6 +2341,7 @@ inline int GpuMixerBank::EndLockstep() {
 }
 
 inline int GpuMixerBank::SlotsHome() {
+  if (GpuMatchBank* mb = st().match) mb->HomeFromDevice(stm_, sink_ && sink_->SilentSlotsAreZero());
   GpuIndirectBank* ib = st().indirect;
   if (!ib) return status();
   ib->SlotsFromDevice(stm_);
@@ -1851,6 +2366,9 @@ inline int GpuMixerBank::Flush() {
     for (int k = 0; k < stm_.num_layer0_mixers; ++k) stm_.mixer_layer0_outputs[k] = o[j++];
     for (int k = 0; k < stm_.num_layer1_mixers; ++k) stm_.mixer_layer1_outputs[k] = o[j++];
     if (j < (size_t)M) stm_.final_mixer_output = o[j];
+    if (track_seen_ && v.match_longest)  // the rows of the mixers whose gate context is longest_match
+      for (uint64_t i = 0; i < v.n; ++i)
+        for (int32_t j : match_cols_) MarkSeen((size_t)j, v.match_longest[i]);
     if (v.ind_active) last_ind_active_.assign(v.ind_active + (v.n - 1) * 2 * (size_t)v.n_ind, v.ind_active + v.n * 2 * (size_t)v.n_ind);
     if (st().lstm) {
       st().lstm->range_on_device_ = true;

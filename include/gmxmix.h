@@ -536,7 +536,9 @@ int gmx_match_learn(gmx_match* mb, int stream, int bit);
  * gmx_indirect_slots_get) and new_bit, the last coded bit, which the next Match::Predict compares with the history
  * (match.cpp:29).  Both belong to the reference's ShortTermMemory checkpoint, not to Match's: gmx_match_import leaves
  * them alone, gmx_match_reset zeroes them, gmx_match_copy copies them.  A caller that restores a stream sets them
- * after the import.  get: values / new_bit nullable. */
+ * after the import.  get: values / new_bit nullable.  set also drops a pending gmx_match_forward of the stream: a bit
+ * that is perceived but never learned (the reference's generation loop: Perceive -> Predict, no Learn) is handed over as
+ * new_bit, and the next forward is its successor's -- no history push, no table entry, no count for the bit in between. */
 int gmx_match_slots_get(gmx_match* mb, int stream, float* values /* [K] */, int* new_bit);
 int gmx_match_slots_set(gmx_match* mb, int stream, const float* values /* [K] */, int new_bit);
 int gmx_match_history_size(gmx_match* mb, int stream, uint64_t* size);   /* LongTermMemory::history.size() */
