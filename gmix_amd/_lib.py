@@ -108,6 +108,8 @@ def lib():
     L.gmx_indirect_bank_bytes.restype = u64
     L.gmx_indirect_forward.argtypes = [vp, i32, vp, u32, vp, vp]
     L.gmx_chain_forward.argtypes = [vp, vp, i32, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.gmx_indirect_attach_match.argtypes = [vp, vp, C.POINTER(C.c_int32), i32]
+    L.gmx_chain_forward_match.argtypes = [vp, vp, i32, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gmx_indirect_learn.argtypes = [vp, i32, i32]
     L.gmx_ind_batch_create.argtypes = [C.POINTER(vp), vp, u64]
     L.gmx_ind_batch_destroy.argtypes = [vp]
@@ -260,6 +262,7 @@ ABI_SYMBOLS = [
     "gmx_chainstep_ppm", "gmx_chainstep_bits", "gmx_chainstep_what", "gmx_chainstep_p", "gmx_chainstep_outputs",
     "gmx_chainstep_commit", "gmx_chainstep_step", "gmx_chainstep_launch", "gmx_chainstep_wait",
     "gmx_chainstep_attach_match", "gmx_chainstep_match_contexts",
+    "gmx_indirect_attach_match", "gmx_chain_forward_match",
     "gmx_group_set_cu_mask", "gmx_indirect_set_cu_mask", "gmx_lstm_set_cu_mask",
     "gmx_match_create", "gmx_match_destroy", "gmx_match_n_streams", "gmx_match_n_models", "gmx_match_bank_bytes",
     "gmx_match_reset", "gmx_match_sync", "gmx_match_set_cu_mask", "gmx_match_batch_create", "gmx_match_batch_destroy",

@@ -1840,6 +1840,149 @@ extern "C" int gmx_chain_forward(gmx_indirect* ib, gmx_group* g, int stream, con
   return GMX_OK;
 }
 
+// ---- Match models + Indirect models -> mixers, one host round trip -------------------------------------
+// gmx_match_forward, then gmx_chain_forward with the Match models' slots, active flags and longest_match put into the
+// mixers' inputs -- but when the Match bank is attached to the Indirect bank (gmx_indirect_attach_match) and the
+// conditions of gmx_chain_forward's fused path hold, the Match models step in lanes 56..63 of the Indirect models'
+// session wave (gmx_indirect_session_kernel<true>), which writes all of it into the mixers' payload before it rings
+// them: ONE command, ONE wait.  A learn gmx_match_learn noted rides in the same command (GmxIndMbCmd::match_what).
+extern "C" int gmx_chain_forward_match(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
+                                       const uint32_t* match_contexts, uint32_t bit_context, const float* predictions,
+                                       const int32_t* active_models, int n_active, const uint32_t* contexts,
+                                       float* p_final, float* out_all, float* ind_predictions, uint8_t* ind_active,
+                                       float* match_predictions, uint8_t* match_active, uint32_t* longest_match) {
+  if (!ib || !g || stream < 0 || stream >= ib->S || stream >= g->S || !ind_contexts || !match_contexts ||
+      !predictions || !contexts || bit_context > 254u)
+    return GMX_ERR_INVALID;
+  if (n_active > 0 && !active_models) return GMX_ERR_INVALID;
+  gmx_match* const mb = ib->match;
+  if (!mb) return GMX_ERR_STATE;  // no bank attached: the caller's own gmx_match_forward + gmx_chain_forward
+  const GmxTopoDev& t = g->topo;
+  const int K = ib->dev.k, KM = mb->dev.k;
+  // ---- everything that can be refused is refused before either bank moves
+  if (n_active > t.n) return GMX_ERR_INVALID;
+  for (int i = 0; i < n_active; ++i)
+    if (active_models[i] < 0 || active_models[i] >= t.n) return GMX_ERR_INVALID;
+  uint32_t own[GMX_MAX_INPUTS / 32] = {0};  // the active-mask bits of the Indirect and the Match models' slots
+  for (int i = 0; i < K; ++i) {
+    const int a = ib->dev.m[i].slot_a, b = ib->dev.m[i].slot_b;
+    if (a < 0 || a >= t.n || b < 0 || b >= t.n) return GMX_ERR_INVALID;
+    own[a >> 5] |= 1u << (a & 31);
+    own[b >> 5] |= 1u << (b & 31);
+  }
+  for (int i = 0; i < KM; ++i) {
+    const int a = mb->dev.m[i].slot;
+    if (a < 0 || a >= t.n) return GMX_ERR_INVALID;
+    own[a >> 5] |= 1u << (a & 31);
+  }
+  for (int c = 0; c < ib->match_n_cols; ++c)
+    if (ib->match_cols[c] >= t.m) return GMX_ERR_INVALID;
+  if (mb->fwd_done[stream]) return GMX_ERR_STATE;  // Match::Predict moves state: one per bit
+  HIPCHK(hipSetDevice(g->device));
+  float ip_[2 * GMX_IND_MAX_MODELS], mp_[GMX_MATCH_MAX_MODELS];  // (no allocation on a per-bit path)
+  uint8_t ia_[2 * GMX_IND_MAX_MODELS], ma_[GMX_MATCH_MAX_MODELS];
+  uint32_t lm = 0;
+  const size_t n2 = (size_t)2 * K;
+  auto results_out = [&]() {
+    if (ind_predictions) memcpy(ind_predictions, ip_, n2 * 4);
+    if (ind_active) memcpy(ind_active, ia_, n2);
+    if (match_predictions) memcpy(match_predictions, mp_, (size_t)KM * 4);
+    if (match_active) memcpy(match_active, ma_, (size_t)KM);
+    if (longest_match) *longest_match = lm;
+  };
+  if (ib->device == g->device && ib->use_sessions && g->use_sessions && group_is_stock(g) && n_active >= 0 && K <= 56) {
+    const int noted = mb->noted[stream];
+    // (a launch-path learn of this bank that nobody has waited for yet: the wave reads what it writes)
+    if (hipStreamQuery(mb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(mb->stream));
+    (void)hipGetLastError();
+    int rc = session_forward_prepare(g, stream, predictions, active_models, n_active, contexts, own);
+    if (rc == GMX_OK) {
+      GmxSession* se = g->sessions[stream];
+      GmxIndMatchCmd mcmd;
+      mcmd.ctx = match_contexts;
+      mcmd.what = kMatchStepPredict | kMatchStepTakeCtx;
+      if (noted) mcmd.what |= kMatchStepLearn | ((uint32_t)(noted - 1) << GMX_IND_MB_MATCH_BIT_SHIFT);
+      mcmd.predictions = mp_;
+      mcmd.active = ma_;
+      mcmd.longest_match = &lm;
+      rc = ind_session_forward(ib, stream, ind_contexts, bit_context, ip_, ia_, se->word, se->slot, se->mc, &mcmd);
+      if (rc == GMX_OK) {
+        ib->fwd_done[stream] = 2;
+        mb->noted[stream] = 0;  // (it went with the command)
+        mb->fwd_done[stream] = 2;
+        mb->fwd_bc[stream] = bit_context;
+        rc = session_forward_finish(g, stream, p_final, out_all);
+        if (rc == GMX_OK) g->fwd_done[stream] = 2;
+      } else {
+        // the Indirect side did not take the command (nothing of it was published): both banks' forwards as launches,
+        // their results into the payload by the host, and the mixers rung from here
+        int rc2 = rc;
+        if (rc == GMX_ERR_STATE) {
+          rc2 = match_flush_noted(mb, stream);
+          if (rc2 == GMX_OK) rc2 = match_forward_launch(mb, stream, match_contexts, bit_context, mp_, ma_, &lm);
+          if (rc2 == GMX_OK) rc2 = gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ip_, ia_);
+        }
+        if (rc2 == GMX_OK) {
+          GmxMbPayload* pay = &se->mc->slot[se->slot];
+          for (int i = 0; i < K; ++i) {
+            const int sl[2] = {ib->dev.m[i].slot_a, ib->dev.m[i].slot_b};
+            for (int h = 0; h < 2; ++h) {
+              pay->pred[sl[h]] = ip_[2 * i + h];
+              if (ia_[2 * i + h]) pay->mask[sl[h] >> 5] = pay->mask[sl[h] >> 5] | (1u << (sl[h] & 31));
+            }
+          }
+          for (int i = 0; i < KM; ++i) {
+            const int sl = mb->dev.m[i].slot;
+            pay->pred[sl] = mp_[i];
+            if (ma_[i]) pay->mask[sl >> 5] = pay->mask[sl >> 5] | (1u << (sl & 31));
+          }
+          for (int c = 0; c < ib->match_n_cols; ++c) pay->ctx[ib->match_cols[c]] = lm;
+          session_ring(se);
+          rc2 = session_forward_finish(g, stream, p_final, out_all);
+          if (rc2 == GMX_OK) g->fwd_done[stream] = 2;
+        } else {
+          // the prepared command still goes (it carries the learn gmx_bank_learn noted, and the mailbox
+          // protocol expects an answer to the word it was given); its forward is not one to learn from
+          session_ring(se);
+          if (session_forward_finish(g, stream, nullptr, nullptr) == GMX_OK) se->fwd_live = false;
+        }
+        rc = rc2;
+      }
+      if (rc == GMX_OK) results_out();
+      return rc;
+    }
+    if (rc != GMX_ERR_STATE) return rc;  // GMX_ERR_STATE: no session slot for the mixers, the calls one by one instead
+  }
+  // ---- the two calls, the host in between.  The Match forward on the launch path: the stream's wave, if one runs,
+  // keeps nothing of its Match state and steps it only when told to, so it need not stop.
+  int rc = match_flush_noted(mb, stream);
+  if (rc) return rc;
+  rc = match_forward_launch(mb, stream, match_contexts, bit_context, mp_, ma_, &lm);
+  if (rc) return rc;
+  float pr[GMX_MAX_INPUTS];
+  int32_t act[GMX_MAX_INPUTS];
+  uint32_t cx[GMX_MAX_MIXERS];
+  memcpy(pr, predictions, (size_t)t.n * sizeof(float));
+  memcpy(cx, contexts, (size_t)t.m * sizeof(uint32_t));
+  for (int c = 0; c < ib->match_n_cols; ++c) cx[ib->match_cols[c]] = lm;
+  int na = n_active;
+  if (n_active >= 0) {
+    uint32_t on[GMX_MAX_INPUTS / 32] = {0};
+    for (int i = 0; i < n_active; ++i) on[active_models[i] >> 5] |= 1u << (active_models[i] & 31);
+    for (int w = 0; w < GMX_MAX_INPUTS / 32; ++w) on[w] &= ~own[w];
+    for (int i = 0; i < KM; ++i)
+      if (ma_[i]) on[mb->dev.m[i].slot >> 5] |= 1u << (mb->dev.m[i].slot & 31);
+    na = 0;
+    for (int idx = 0; idx < t.n; ++idx)  // ascending, like ShortTermMemory::active_models
+      if ((on[idx >> 5] >> (idx & 31)) & 1u) act[na++] = idx;
+  }
+  for (int i = 0; i < KM; ++i) pr[mb->dev.m[i].slot] = mp_[i];
+  rc = gmx_chain_forward(ib, g, stream, ind_contexts, bit_context, pr, act, na, cx, p_final, out_all, ip_, ia_);
+  if (rc) return rc;
+  results_out();
+  return GMX_OK;
+}
+
 extern "C" int gmx_lstm_set_cu_mask(gmx_lstm* l, const uint32_t* mask, int n_words) {
   if (!l || n_words < 0 || (n_words > 0 && !mask)) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(l->device));

@@ -63,6 +63,7 @@ struct gmx_chainstep {
   gmx_indirect* ib = nullptr;
   gmx_lstm* l = nullptr;
   gmx_match* mb = nullptr;         // gmx_chainstep_attach_match: the Match models step on the device too
+  bool mb_gone = false;            // ... and that bank has been destroyed: the captured steps would write freed memory
   int n_mcols = 0;                 // mixer context columns that receive longest_match
   int32_t mcols[GMX_MATCH_MAX_CTX_COLS] = {};
   uint32_t* mctx = nullptr;        // host view [S][K_match]: the Match models' context words (room for 8 a stream)
@@ -116,8 +117,21 @@ struct gmx_chainstep {
 
 static size_t cs_round(size_t n) { return (n + 255) / 256 * 256; }
 
+static void chainstep_match_gone(gmx_chainstep* cs) {
+  if (cs->g) {
+    (void)hipSetDevice(cs->g->device);
+    if (cs->g->stream) (void)hipStreamSynchronize(cs->g->stream);  // (a step in flight still writes the bank)
+  }
+  cs->mb = nullptr;
+  cs->mb_gone = true;
+}
+
 extern "C" void gmx_chainstep_destroy(gmx_chainstep* cs) {
   if (!cs) return;
+  if (cs->mb) {
+    auto& v = cs->mb->chainsteps;
+    v.erase(std::remove(v.begin(), v.end(), cs), v.end());
+  }
   if (cs->g) {
     (void)hipSetDevice(cs->g->device);
     if (cs->g->stream) (void)hipStreamSynchronize(cs->g->stream);
@@ -540,6 +554,7 @@ extern "C" int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, cons
                                           int n_ctx_columns) {
   if (!cs || !cs->g || !mb) return GMX_ERR_INVALID;
   if (cs->mb || cs->steps != 0 || cs->in_flight) return GMX_ERR_STATE;  // once, before the first step
+  if (mb->host) return GMX_ERR_STATE;  // (its streams ride in per-bit session waves: gmx_indirect_attach_match)
   gmx_group* g = cs->g;
   const GmxTopoDev& t = g->topo;
   if (mb->S != cs->S || mb->device != g->device || t.mask_words > GMX_MATCH_MAX_MASK_WORDS) return GMX_ERR_INVALID;
@@ -554,6 +569,7 @@ extern "C" int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, cons
   HIPCHK(hipStreamSynchronize(mb->stream));
   HIPCHK(hipStreamSynchronize(g->stream));
   cs->mb = mb;
+  mb->chainsteps.push_back(cs);
   cs->n_mcols = n_ctx_columns;
   for (int c = 0; c < n_ctx_columns; ++c) cs->mcols[c] = ctx_columns[c];
   cs->m_bc.assign(cs->S, 0);
@@ -565,6 +581,7 @@ extern "C" int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, cons
   const hipError_t e = cs_capture(cs);
   if (e != hipSuccess) {  // (the object cannot step any more: no graph of it is whole)
     cs->mb = nullptr;
+    mb->chainsteps.pop_back();
     cs->up.n -= 1;
     return e == hipErrorOutOfMemory ? GMX_ERR_NOMEM : hip_fail(e, "gmx_chainstep_attach_match: capture");
   }
@@ -631,7 +648,7 @@ static double cs_now() {
 
 extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
   if (!cs || !cs->g) return GMX_ERR_INVALID;
-  if (cs->in_flight) return GMX_ERR_STATE;
+  if (cs->in_flight || cs->mb_gone) return GMX_ERR_STATE;
   gmx_group* g = cs->g;
   const int S = cs->S;
   bool any = false, opens = false;

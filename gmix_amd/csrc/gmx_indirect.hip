@@ -469,10 +469,32 @@ extern "C" hipError_t gmx_launch_indirect_kernel(const GmxIndDev* dv, const GmxI
 // wave leaves -- writing the logit tables and the slot values back -- on GMX_MB_STOP or after
 // `idle_ticks` of s_memrealtime without a command.  `replay_forward`: started between the forward and
 // the learn of a bit, it recomputes the forward from the contexts still in the mailbox first.
+//
+// WITH_MATCH (gmx_indirect_attach_match): the stream's Match models (gmx_match_step.h) in lanes 56..63 -- idle
+// otherwise (the host sees to K <= 56), and exactly one DPP group of eight -- as in gmx_indirect_step_kernel.  What
+// they do in a command is in the payload slot's match_what (GMX_MATCH_STEP_* and the Learn's coded bit in bit 8, so
+// that a Match learn does not depend on the command word); only a chained forward carries one.  `ma` is the step's
+// arguments for "stream 0" of this wave: banks / hist are the stream's own, and ctx / bc / bits / mx_pred / mx_ctx
+// are pointed into the two mailboxes command by command.  Their three trips ride beside the wave's own: state and
+// record with the mailbox read; both probabilities, the count and the table entry with the Indirect models' table
+// load; the history byte behind that.  Their active bits join the four mask words in LDS; longest_match goes into
+// the mixers' gate contexts before their doorbell is rung.
+//   Nothing of a stream's Match state lives outside the bank, so a replayed forward (the first pass has stored what
+// Match::Predict moved), an idle exit, an eviction and a stop have nothing of theirs to redo or to write back.
+//   Visibility: the wave is alone in its workgroup and reads back only what it stored itself -- the regime of
+// gmx_match_kernel -- but across commands and, for the stream state, across lanes: the history byte lane 56 pushes
+// is history[cur_match_] of any of the eight lanes at a later byte; the table entry a lane writes is the one it reads
+// at a later byte; the GmxMatchStreamState lane 56 stores is loaded by lanes 57..63 at the very next command.  Every
+// command ends with s_waitcnt vmcnt(0) -- all stores of all 64 lanes have reached L2, the one copy a CU's vector
+// loads are served from once its L1 line is gone -- and the next command begins behind the acquire fence after the
+// poll, which invalidates L1: no load of command n+1 can be served from a line older than the stores of command n.
+// Inside a command nothing is read back from memory: the hand-overs go through registers (gmx_match_step.h).
 // ---------------------------------------------------------------------------------------
+template <bool WITH_MATCH>
 __global__ void __launch_bounds__(64)
 gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, int stream, GmxIndMbCmd* mc,
-                            GmxIndMbReply* mr, unsigned long long idle_ticks, int replay_forward) {
+                            GmxIndMbReply* mr, unsigned long long idle_ticks, int replay_forward,
+                            const GmxMatchDev* __restrict__ mdv, const GmxMatchStepArgs ma0) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x;
   const int K = dv->k;
@@ -526,6 +548,33 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
     const bool with_learn = cmd == GMX_MB_LEARN0 || cmd == GMX_MB_LEARN1 || cmd == GMX_MB_LEARN0_FWD ||
                             cmd == GMX_MB_LEARN1_FWD;
     const bool with_forward = cmd == GMX_MB_FORWARD || cmd == GMX_MB_LEARN0_FWD || cmd == GMX_MB_LEARN1_FWD;
+    // ---- the Match lanes' trip 1, beside the rest of the mailbox read (a replayed forward: they sit it out)
+    GmxMatchStepLane mt;
+    // (the step's arguments, field by field, and without the column list: a local copy that the step indexes by a
+    // run-time count lands in scratch -- longest_match is stored below, with the columns read from the kernel argument)
+    GmxMatchStepArgs ma;
+    ma.banks = ma0.banks;
+    ma.hist = ma0.hist;
+    ma.what = nullptr;
+    ma.mx_mask = nullptr;
+    ma.mx_ctx = nullptr;
+    ma.mx_n_pad = ma.mx_mask_words = ma.mx_m = 0;
+    ma.n_streams = 1;
+    ma.n_ctx_cols = 0;
+    uint32_t mwhat = 0;
+    if (WITH_MATCH) {
+      if (with_forward && !replay && vc->chain_word)
+        mwhat = __builtin_amdgcn_readfirstlane(vc->match_what[slot]) & 0x10bu;
+      if (mwhat & 3u) {  // (wave-uniform)
+        GmxMbCmd* const mmc = (GmxMbCmd*)vc->chain_mc;
+        GmxMbPayload* const mp = &mmc->slot[vc->chain_slot & 1u];
+        ma.ctx = mc->match_ctx[slot];
+        ma.bc = &mc->bit_context[slot];
+        ma.bits = (const uint8_t*)&mc->match_what[slot] + 1;  // bit 8 of the word
+        ma.mx_pred = mp->pred;
+        gmx_match_step_begin(mt, mdv, ma, 0, lane - 56, lane >= 56, mwhat);
+      }
+    }
     if (with_learn && have_fwd) {
       // ---- Indirect::Learn (indirect.cpp:48-69) on the entry the forward latched ------------
       const int bit = (cmd == GMX_MB_LEARN1 || cmd == GMX_MB_LEARN1_FWD) ? 1 : 0;
@@ -547,8 +596,16 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
       const uint32_t bcu = vc->bit_context[slot];
       idx = ((ctx << 8) + bcu) % d.size;  // indirect.cpp:31-32, 32-bit wrap
       uint32_t ev;
-      asm volatile("s_waitcnt vmcnt(0)\n\tglobal_load_ushort %0, %1, off\n\ts_waitcnt vmcnt(0)"
-                   : "=&v"(ev) : "v"(tab + idx) : "memory");  // behind the entry store of the learn above
+      if (WITH_MATCH && (mwhat & 3u)) {
+        // ---- trip 2: the Match lanes' loads go out first, the table entry behind them, ONE wait for all
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // behind the entry store of the learn above
+        gmx_match_step_fetch(mt);
+        asm volatile("global_load_ushort %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(ev) : "v"(tab + idx) : "memory");
+        gmx_match_step_look(mt);  // ---- trip 3: the history byte, under the Indirect models' LDS reads and stores
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)\n\tglobal_load_ushort %0, %1, off\n\ts_waitcnt vmcnt(0)"
+                     : "=&v"(ev) : "v"(tab + idx) : "memory");  // behind the entry store of the learn above
+      }
       e = ev;
       const uint32_t ns = e & 255u, rm = e >> 8;
       const float qa = nsp[ns], qb = rmp[rm];
@@ -579,6 +636,19 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
             mp->pred[d.slot_b] = vb;
             if ((act_a >> lane) & 1ull) atomicOr(&mwl[d.slot_a >> 5], 1u << (d.slot_a & 31));
             if ((act_b >> lane) & 1ull) atomicOr(&mwl[d.slot_b >> 5], 1u << (d.slot_b & 31));
+          }
+          if (WITH_MATCH && (mwhat & 3u)) {
+            // the Match models' slots and longest_match into the payload, their stores to the bank, their mask bits
+            const uint32_t lm = gmx_match_step_finish(mt, ma, 0);
+            if (mt.active) atomicOr(&mwl[(uint32_t)mt.md.slot >> 5], 1u << ((uint32_t)mt.md.slot & 31u));
+            if (mt.do_pred) {
+              vr->match_pred[lane - 56] = mt.slot_value;
+              vr->match_active[lane - 56] = mt.active ? 1u : 0u;
+              if (mt.lead) {
+                vr->longest_match = lm;
+                for (int c = 0; c < ma0.n_ctx_cols; ++c) mp->ctx[ma0.ctx_cols[c]] = lm;
+              }
+            }
           }
           if (lane < 4) mp->mask[lane] = mp->mask[lane] | mwl[lane];  // the host left these bits clear
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -619,13 +689,38 @@ extern "C" hipError_t gmx_launch_indirect_session(const GmxIndDev* dv, uint8_t* 
   (void)hipGetLastError();
   static unsigned allowed = 48u * 1024u;
   if (lds_bytes > allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel,
+    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel<false>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
     allowed = lds_bytes;
   }
-  hipLaunchKernelGGL(gmx_indirect_session_kernel, dim3(1), dim3(64), lds_bytes, stream, dv, banks, stream_idx, mc,
-                     mr, idle_ticks, replay_forward);
+  GmxMatchStepArgs mnone;
+  memset(&mnone, 0, sizeof mnone);
+  hipLaunchKernelGGL(gmx_indirect_session_kernel<false>, dim3(1), dim3(64), lds_bytes, stream, dv, banks, stream_idx,
+                     mc, mr, idle_ticks, replay_forward, (const GmxMatchDev*)nullptr, mnone);
+  return hipGetLastError();
+}
+// ... with the stream's Match models in lanes 56..63: margs->banks / hist are the STREAM's (the wave steps them as
+// stream 0), n_ctx_cols / ctx_cols the mixers' gate-context columns that receive longest_match; every other pointer
+// is set by the wave.  k_ind <= 56 is the caller's to see to (gmx_indirect_attach_match); checked here all the same.
+extern "C" hipError_t gmx_launch_indirect_session_match(const GmxIndDev* dv, int k_ind, uint8_t* banks, int stream_idx,
+                                                        GmxIndMbCmd* mc, GmxIndMbReply* mr,
+                                                        unsigned long long idle_ticks, int replay_forward,
+                                                        const GmxMatchDev* mdv, const GmxMatchStepArgs* margs,
+                                                        unsigned lds_bytes, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (k_ind > 56 || !mdv || !margs || !margs->banks || !margs->hist || margs->n_ctx_cols < 0 ||
+      margs->n_ctx_cols > GMX_MATCH_MAX_CTX_COLS)
+    return hipErrorInvalidValue;
+  static unsigned allowed = 48u * 1024u;
+  if (lds_bytes > allowed) {
+    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel<true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    allowed = lds_bytes;
+  }
+  hipLaunchKernelGGL(gmx_indirect_session_kernel<true>, dim3(1), dim3(64), lds_bytes, stream, dv, banks, stream_idx,
+                     mc, mr, idle_ticks, replay_forward, mdv, *margs);
   return hipGetLastError();
 }
 

@@ -42,8 +42,33 @@ struct gmx_indirect {
   std::vector<struct GmxIndSession*> sessions;  // per-bit sessions (gmx_indirect_session_kernel), per stream
   bool use_sessions = true;
   struct GmxIndCkptState* ckpt = nullptr;  // gmx_indirect_group_export / _import: chunk list and staging (gmx_ind_ckpt.inc), lazily
+  // gmx_indirect_attach_match: the streams of this Match bank ride in lanes 56..63 of the session waves.  What a
+  // wave needs of the bank is copied here at the attach (gmx_match.inc comes later in the translation unit); the two
+  // objects register with each other, and whichever is destroyed first detaches (match_host_detach).
+  gmx_match* match = nullptr;
+  const GmxMatchDev* match_dev_d = nullptr;
+  uint8_t* match_banks = nullptr;
+  uint8_t* match_hist = nullptr;
+  uint64_t match_bank_bytes = 0, match_hist_cap = 0;
+  int match_k = 0, match_n_cols = 0;
+  int32_t match_slot[GMX_MATCH_MAX_MODELS] = {};
+  int32_t match_cols[GMX_MATCH_MAX_CTX_COLS] = {};
 };
 static void ind_ckpt_free(gmx_indirect* ib);
+static int match_host_detach(gmx_match* mb);  // gmx_match.inc
+static_assert(sizeof(((GmxIndMbCmd*)nullptr)->match_ctx[0]) == GMX_MATCH_MAX_MODELS * 4 &&
+                  sizeof(((GmxIndMbReply*)nullptr)->match_pred) == GMX_MATCH_MAX_MODELS * 4,
+              "the Match fields of the Indirect mailbox hold one lane group");
+
+static const uint32_t kMatchStepLearn = 1u, kMatchStepPredict = 2u, kMatchStepTakeCtx = 8u;  // GMX_MATCH_STEP_*
+// What the Match lanes do in a chained forward, and what they answer (ind_session_forward).
+struct GmxIndMatchCmd {
+  const uint32_t* ctx;     // [K_match]
+  uint32_t what;           // GMX_MATCH_STEP_* | coded bit << GMX_IND_MB_MATCH_BIT_SHIFT
+  float* predictions;      // [K_match], nullable
+  uint8_t* active;         // [K_match], nullable
+  uint32_t* longest_match; // nullable
+};
 
 // ---- per-bit sessions: gmx_indirect_forward / gmx_indirect_learn without a kernel launch per call -----
 // The host side mirrors gmx_session.inc (same mailbox protocol, same bounded waits, the same count of open
@@ -87,6 +112,10 @@ hipError_t gmx_launch_ind_synth_kernel(const GmxIndSynthArgs* args, hipStream_t 
 hipError_t gmx_launch_indirect_session(const GmxIndDev* dv, uint8_t* banks, int stream_idx, GmxIndMbCmd* mc,
                                        GmxIndMbReply* mr, unsigned long long idle_ticks, int replay_forward,
                                        unsigned lds_bytes, hipStream_t stream);
+hipError_t gmx_launch_indirect_session_match(const GmxIndDev* dv, int k_ind, uint8_t* banks, int stream_idx,
+                                             GmxIndMbCmd* mc, GmxIndMbReply* mr, unsigned long long idle_ticks,
+                                             int replay_forward, const GmxMatchDev* mdv, const GmxMatchStepArgs* margs,
+                                             unsigned lds_bytes, hipStream_t stream);
 }
 
 static void ind_batch_free(gmx_ind_batch* b) {
@@ -112,6 +141,7 @@ static void ind_batch_free(gmx_ind_batch* b) {
 extern "C" void gmx_indirect_destroy(gmx_indirect* ib) {
   if (!ib) return;
   (void)hipSetDevice(ib->device);
+  if (ib->match) (void)match_host_detach(ib->match);  // (stops the sessions; a noted Match learn takes the launch path)
   ind_sessions_free(ib);
   if (ib->stream) (void)hipStreamSynchronize(ib->stream);
   if (ib->one) {
@@ -519,8 +549,21 @@ static int ind_session_start(gmx_indirect* ib, int s) {
   ind_session_note_done(se);
   __atomic_store_n(&se->mb->state, GMX_MB_RUNNING, __ATOMIC_RELEASE);
   se->launched = true;
-  HIPCHK(gmx_launch_indirect_session(ib->dev_d, ib->banks, s, se->mc, se->mb, kIdleTicks,
-                                     se->fwd_live ? 1 + (int)se->live_slot : 0, ib->lds_bytes, se->stream));
+  const int replay = se->fwd_live ? 1 + (int)se->live_slot : 0;
+  if (ib->match) {  // the stream's Match models in lanes 56..63: the wave steps them as "stream 0" of these arguments
+    GmxMatchStepArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.banks = ib->match_banks + (uint64_t)s * ib->match_bank_bytes;
+    ma.hist = ib->match_hist + (uint64_t)s * ib->match_hist_cap;
+    ma.n_ctx_cols = ib->match_n_cols;
+    for (int c = 0; c < ib->match_n_cols; ++c) ma.ctx_cols[c] = ib->match_cols[c];
+    ma.n_streams = 1;
+    HIPCHK(gmx_launch_indirect_session_match(ib->dev_d, ib->dev.k, ib->banks, s, se->mc, se->mb, kIdleTicks, replay,
+                                             ib->match_dev_d, &ma, ib->lds_bytes, se->stream));
+    return GMX_OK;
+  }
+  HIPCHK(gmx_launch_indirect_session(ib->dev_d, ib->banks, s, se->mc, se->mb, kIdleTicks, replay, ib->lds_bytes,
+                                     se->stream));
   return GMX_OK;
 }
 
@@ -700,7 +743,8 @@ static void ind_sessions_free(gmx_indirect* ib) {
 // chain_mc (payload slot chain_slot) and rings it with chain_word (GmxIndMbCmd); 0 = an ordinary forward.
 static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts, uint32_t bit_context,
                                float* predictions, uint8_t* active, uint32_t chain_word = 0,
-                               uint32_t chain_slot = 0, void* chain_mc = nullptr) {
+                               uint32_t chain_slot = 0, void* chain_mc = nullptr,
+                               const GmxIndMatchCmd* match = nullptr) {
   {
     // a noted learn rides along only if the wave that made its forward is still there
     GmxIndSession* se0 = s < (int)ib->sessions.size() ? ib->sessions[s] : nullptr;
@@ -723,6 +767,14 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
   se->slot ^= 1u;
   memcpy(se->mc->ctx[se->slot], img, sizeof img);
   se->mc->bit_context[se->slot] = bit_context;
+  if (ib->match) {  // (every forward says what the Match lanes do: nothing, unless this is their chained forward)
+    if (match) {
+      uint32_t mimg[GMX_MATCH_MAX_MODELS] = {0};
+      memcpy(mimg, match->ctx, (size_t)ib->match_k * 4);
+      memcpy(se->mc->match_ctx[se->slot], mimg, sizeof mimg);
+    }
+    se->mc->match_what[se->slot] = (match && chain_word) ? match->what : 0u;
+  }
   se->mc->chain_slot = chain_slot;
   se->mc->chain_mc = (uint64_t)(uintptr_t)chain_mc;
   se->mc->chain_word = chain_word;
@@ -743,6 +795,13 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
       active[2 * i] = (uint8_t)((a >> i) & 1u);
       active[2 * i + 1] = (uint8_t)((b >> i) & 1u);
     }
+  }
+  if (ib->match && match && chain_word) {
+    for (int i = 0; i < ib->match_k; ++i) {
+      if (match->predictions) match->predictions[i] = se->mb->match_pred[i];
+      if (match->active) match->active[i] = (uint8_t)(se->mb->match_active[i] != 0u);
+    }
+    if (match->longest_match) *match->longest_match = se->mb->longest_match;
   }
   return GMX_OK;
 }

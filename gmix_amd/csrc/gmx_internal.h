@@ -231,7 +231,16 @@ struct GmxIndMbCmd {       // host -> device: fine-grained device memory behind 
   // of the forward whose learn is still to come stays intact while the next is written, so a wave
   // restarted in between can recompute that forward
   uint32_t ctx[2][GMX_IND_MAX_MODELS];
+  // The stream's Match models riding in lanes 56..63 (gmx_indirect_attach_match), per payload slot: their context
+  // words, and what they do in the command: GMX_MATCH_STEP_LEARN | _PREDICT | _TAKE_CTX (gmx_match_step.h), and in
+  // bit 8 the coded bit of that Learn -- here, not in the command word: a Match learn does not depend on what
+  // gmx_indirect_learn was told.  0: they sit the command out (as they do in every command that is not a chained
+  // forward, and in a replayed one).
+  uint32_t match_ctx[2][8];  // [GMX_MATCH_MAX_MODELS]
+  uint32_t match_what[2];
+  uint32_t pad2[6];
 };
+#define GMX_IND_MB_MATCH_BIT_SHIFT 8
 struct GmxIndMbReply {     // device -> host: pinned host memory
   uint32_t done_seq;
   uint32_t state;          // GMX_MB_RUNNING / GMX_MB_EXIT_*
@@ -239,6 +248,11 @@ struct GmxIndMbReply {     // device -> host: pinned host memory
   uint64_t active_a, active_b;  // bit i: model i's "-indirect" / "-run_map" slot was marked active
   uint32_t pad1[8];
   float pred[2 * GMX_IND_MAX_MODELS];  // what the two blackboard slots of model i hold after its Predict
+  // the Match models of a chained forward that carried them: slot values, "marked active", longest_match
+  float match_pred[8];                 // [GMX_MATCH_MAX_MODELS]
+  uint32_t match_active[8];
+  uint32_t longest_match;
+  uint32_t pad2[15];
 };
 
 struct GmxIndRunArgs {

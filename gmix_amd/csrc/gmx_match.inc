@@ -47,7 +47,17 @@ struct gmx_match {
   uint8_t* model_dense_d = nullptr;
   uint64_t* model_off_d = nullptr;
   uint64_t gck_ops = 0;  // launches, transfers, synchronisations, allocations of the group checkpoint calls so far
+  // gmx_indirect_attach_match: the bank's streams ride in the per-bit session waves of `host` (lanes 56..63 of
+  // gmx_indirect_session_kernel<true>).  fwd_done[s] == 2: the stream's newest forward went that way, and its
+  // gmx_match_learn only notes the bit (noted[s] = 1 + bit), which travels with the next chained forward.  Nothing of
+  // a stream's state lives outside the bank, so "up to date" means: no wave running, no learn noted (match_settle).
+  gmx_indirect* host = nullptr;
+  std::vector<uint8_t> noted;
+  std::vector<gmx_chainstep*> chainsteps;  // the lock-step objects this bank is attached to, each registered here:
+                                           // whichever of the two is destroyed first tells the other
 };
+static void chainstep_match_gone(gmx_chainstep* cs);  // gmx_chainstep.inc
+static int match_settle(gmx_match* mb);
 
 extern "C" {
 hipError_t gmx_launch_match_kernel(const GmxMatchDev* dv, const GmxMatchRunArgs* args, hipStream_t stream);
@@ -81,6 +91,9 @@ static void match_batch_free(gmx_match_batch* b) {
 extern "C" void gmx_match_destroy(gmx_match* mb) {
   if (!mb) return;
   (void)hipSetDevice(mb->device);
+  if (mb->host) (void)match_host_detach(mb);  // (no wave of the host's reads this bank any more)
+  for (gmx_chainstep* cs : mb->chainsteps) chainstep_match_gone(cs);
+  mb->chainsteps.clear();
   if (mb->stream) (void)hipStreamSynchronize(mb->stream);
   if (mb->one) {
     match_batch_free(mb->one);
@@ -102,6 +115,11 @@ extern "C" void gmx_match_destroy(gmx_match* mb) {
 extern "C" int gmx_match_reset(gmx_match* mb) {
   if (!mb) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(mb->device));
+  if (mb->host) {  // (a noted learn is void with the state it would have moved)
+    int rcs = ind_sessions_close(mb->host);
+    if (rcs) return rcs;
+  }
+  std::fill(mb->noted.begin(), mb->noted.end(), 0);
   HIPCHK(gmx_launch_match_init(mb->dev_d, mb->banks, 0, mb->S, mb->stream));
   HIPCHK(hipStreamSynchronize(mb->stream));
   std::fill(mb->fwd_done.begin(), mb->fwd_done.end(), 0);
@@ -158,6 +176,7 @@ extern "C" int gmx_match_create(gmx_match** out, const gmx_match_desc* models, i
   mb->dev = d;
   mb->fwd_done.assign(n_streams, 0);
   mb->fwd_bc.assign(n_streams, 0);
+  mb->noted.assign(n_streams, 0);
   mb->hist_bound.assign(n_streams, 0);
   for (int i = 0; i < n_models; ++i)
     for (uint32_t e = 0; e < d.m[i].table_size; e += GMX_MATCH_CKPT_CHUNK) {
@@ -196,12 +215,20 @@ extern "C" uint64_t gmx_match_bank_bytes(const gmx_match* mb) { return mb ? mb->
 extern "C" int gmx_match_sync(gmx_match* mb) {
   if (!mb) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(mb->device));
+  {
+    int rcs = match_settle(mb);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(mb->stream));
   return GMX_OK;
 }
 extern "C" int gmx_match_set_cu_mask(gmx_match* mb, const uint32_t* mask, int n_words) {
   if (!mb || n_words < 0 || (n_words > 0 && !mask)) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(mb->device));
+  {
+    int rcs = match_settle(mb);
+    if (rcs) return rcs;
+  }
   return stream_with_cu_mask(&mb->stream, mask, n_words);
 }
 
@@ -441,6 +468,8 @@ extern "C" int gmx_match_run_ragged(gmx_match* mb, gmx_match_batch* b, const uin
   int rc = match_into_ok(mb, into, ctx_columns, n_ctx_columns);
   if (rc) return rc;
   HIPCHK(hipSetDevice(mb->device));
+  rc = match_settle(mb);
+  if (rc) return rc;
   uint64_t maxn = 0;
   bool same = true;
   std::vector<uint64_t> add(mb->S);
@@ -462,6 +491,8 @@ extern "C" int gmx_match_run(gmx_match* mb, gmx_match_batch* b, uint64_t n_bits,
   int rc = match_into_ok(mb, into, ctx_columns, n_ctx_columns);
   if (rc) return rc;
   HIPCHK(hipSetDevice(mb->device));
+  rc = match_settle(mb);
+  if (rc) return rc;
   std::vector<uint64_t> add(mb->S, (n_bits + 7) / 8);
   rc = match_reserve(mb, 0, mb->S, add.data());
   if (rc) return rc;
@@ -484,11 +515,9 @@ static int match_ensure_one(gmx_match* mb) {
   return GMX_OK;
 }
 
-extern "C" int gmx_match_forward(gmx_match* mb, int stream, const uint32_t* contexts, uint32_t bit_context,
-                                 float* predictions, uint8_t* active, uint32_t* longest_match) {
-  if (!mb || stream < 0 || stream >= mb->S || !contexts || bit_context > 254u) return GMX_ERR_INVALID;
-  if (mb->fwd_done[stream]) return GMX_ERR_STATE;  // Match::Predict moves state: one per bit
-  HIPCHK(hipSetDevice(mb->device));
+// (the launch path itself; the caller has seen to the protocol and, where the bank is hosted, to the sessions)
+static int match_forward_launch(gmx_match* mb, int stream, const uint32_t* contexts, uint32_t bit_context,
+                                float* predictions, uint8_t* active, uint32_t* longest_match) {
   int rc = match_ensure_one(mb);
   if (rc) return rc;
   gmx_match_batch* b = mb->one;
@@ -512,26 +541,134 @@ extern "C" int gmx_match_forward(gmx_match* mb, int stream, const uint32_t* cont
   return GMX_OK;
 }
 
-extern "C" int gmx_match_learn(gmx_match* mb, int stream, int bit) {
-  if (!mb || stream < 0 || stream >= mb->S || (bit != 0 && bit != 1)) return GMX_ERR_INVALID;
-  if (!mb->fwd_done[stream] || !mb->one) return GMX_ERR_STATE;
+extern "C" int gmx_match_forward(gmx_match* mb, int stream, const uint32_t* contexts, uint32_t bit_context,
+                                 float* predictions, uint8_t* active, uint32_t* longest_match) {
+  if (!mb || stream < 0 || stream >= mb->S || !contexts || bit_context > 254u) return GMX_ERR_INVALID;
+  if (mb->fwd_done[stream]) return GMX_ERR_STATE;  // Match::Predict moves state: one per bit
   HIPCHK(hipSetDevice(mb->device));
+  int rc = match_settle(mb);
+  if (rc) return rc;
+  return match_forward_launch(mb, stream, contexts, bit_context, predictions, active, longest_match);
+}
+
+// The history push and K x Match::Learn of the stream's newest forward, on what that forward left in the bank.
+static int match_learn_launch(gmx_match* mb, int stream, int bit) {
   const uint64_t add = mb->fwd_bc[stream] >= 127u ? 1 : 0;
   int rc = match_reserve(mb, stream, 1, &add);
+  if (rc) return rc;
+  rc = match_ensure_one(mb);
   if (rc) return rc;
   gmx_match_batch* b = mb->one;
   HIPCHK(hipStreamSynchronize(mb->stream));
   b->h_bits[stream] = (uint8_t)bit;
   HIPCHK(hipMemcpyAsync(b->d_bits + stream, b->h_bits + stream, 1, hipMemcpyHostToDevice, mb->stream));
-  rc = match_launch(mb, b, stream, stream, 1, 1, GMX_MATCH_LEARN, nullptr, nullptr, 0, nullptr);
+  return match_launch(mb, b, stream, stream, 1, 1, GMX_MATCH_LEARN, nullptr, nullptr, 0, nullptr);
+}
+
+extern "C" int gmx_match_learn(gmx_match* mb, int stream, int bit) {
+  if (!mb || stream < 0 || stream >= mb->S || (bit != 0 && bit != 1)) return GMX_ERR_INVALID;
+  if (mb->fwd_done[stream] == 2 && mb->host) {
+    // the forward went through a session wave: the bit is noted and travels with the stream's next chained forward
+    // as one command (or takes the launch path when something else needs the bank first: match_settle).  The history
+    // byte it may push is reserved now, as on the launch path: refused here, nothing is noted and no bank moves
+    HIPCHK(hipSetDevice(mb->device));
+    const uint64_t add = mb->fwd_bc[stream] >= 127u ? 1 : 0;
+    int rc = match_reserve(mb, stream, 1, &add);
+    if (rc) return rc;
+    mb->noted[stream] = (uint8_t)(1 + bit);
+    mb->fwd_done[stream] = 0;
+    return GMX_OK;
+  }
+  if (!mb->fwd_done[stream]) return GMX_ERR_STATE;
+  HIPCHK(hipSetDevice(mb->device));
+  int rc = match_learn_launch(mb, stream, bit);
   if (rc) return rc;
   mb->fwd_done[stream] = 0;  // not waited for: every entry point that touches the bank synchronises first
+  return GMX_OK;
+}
+
+// A learn gmx_match_learn noted for stream s: run it through the launch path now.
+static int match_flush_noted(gmx_match* mb, int s) {
+  if (!mb->noted[s]) return GMX_OK;
+  int rc = match_learn_launch(mb, s, mb->noted[s] - 1);
+  if (rc) return rc;
+  mb->noted[s] = 0;
+  return GMX_OK;
+}
+
+// The bank is about to be read or written by something that is not a session wave: the host's waves stop (they keep
+// nothing of a stream's Match state, so there is nothing to write back) and every noted learn is run.
+static int match_settle(gmx_match* mb) {
+  if (!mb->host) return GMX_OK;
+  HIPCHK(hipSetDevice(mb->device));
+  int first = ind_sessions_close(mb->host);
+  for (int s = 0; s < mb->S; ++s) {
+    int rc = match_flush_noted(mb, s);
+    if (rc && !first) first = rc;
+  }
+  return first;
+}
+
+// Either object goes, or the attachment is given up: the waves stop, a noted learn is run, and a forward that went
+// through a wave is from now on an ordinary pending forward of the launch path.
+static int match_host_detach(gmx_match* mb) {
+  if (!mb || !mb->host) return GMX_OK;
+  const int rc = match_settle(mb);
+  for (int s = 0; s < mb->S; ++s)
+    if (mb->fwd_done[s] == 2) mb->fwd_done[s] = 1;
+  gmx_indirect* ib = mb->host;
+  ib->match = nullptr;
+  ib->match_dev_d = nullptr;
+  ib->match_banks = ib->match_hist = nullptr;
+  ib->match_k = ib->match_n_cols = 0;
+  mb->host = nullptr;
+  return rc;
+}
+
+extern "C" int gmx_indirect_attach_match(gmx_indirect* ib, gmx_match* mb, const int32_t* ctx_columns,
+                                         int n_ctx_columns) {
+  if (!ib) return GMX_ERR_INVALID;
+  if (!mb) {  // detach
+    HIPCHK(hipSetDevice(ib->device));
+    return ib->match ? match_host_detach(ib->match) : GMX_OK;
+  }
+  if (ib->dev.k > 56 || mb->S != ib->S || mb->device != ib->device) return GMX_ERR_INVALID;
+  if (n_ctx_columns < 0 || n_ctx_columns > GMX_MATCH_MAX_CTX_COLS || (n_ctx_columns > 0 && !ctx_columns))
+    return GMX_ERR_INVALID;
+  for (int c = 0; c < n_ctx_columns; ++c)
+    if (ctx_columns[c] < 0) return GMX_ERR_INVALID;  // (the upper bound is the mixer group's: checked at the call)
+  for (int i = 0; i < mb->dev.k; ++i)
+    for (int j = 0; j < ib->dev.k; ++j)
+      if (mb->dev.m[i].slot == ib->dev.m[j].slot_a || mb->dev.m[i].slot == ib->dev.m[j].slot_b) return GMX_ERR_INVALID;
+  if (!mb->chainsteps.empty()) return GMX_ERR_STATE;            // one host of its per-bit state at a time
+  if (mb->host && mb->host != ib) return GMX_ERR_STATE;
+  HIPCHK(hipSetDevice(ib->device));
+  int rc = ib->match ? match_host_detach(ib->match) : GMX_OK;  // (another bank, or this one with other columns)
+  if (rc) return rc;
+  rc = ind_sessions_close(ib);  // the waves that run are the build without the Match lanes
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(mb->stream));
+  ib->match = mb;
+  ib->match_dev_d = mb->dev_d;
+  ib->match_banks = mb->banks;
+  ib->match_hist = mb->hist;
+  ib->match_bank_bytes = mb->dev.bank_bytes;
+  ib->match_hist_cap = mb->dev.hist_cap;
+  ib->match_k = mb->dev.k;
+  ib->match_n_cols = n_ctx_columns;
+  for (int i = 0; i < mb->dev.k; ++i) ib->match_slot[i] = mb->dev.m[i].slot;
+  for (int c = 0; c < n_ctx_columns; ++c) ib->match_cols[c] = ctx_columns[c];
+  mb->host = ib;
   return GMX_OK;
 }
 
 // ---- what the bank carries of ShortTermMemory ------------------------------------------------
 static int match_read_states(gmx_match* mb, int stream, GmxMatchModelState* ms, GmxMatchStreamState* ss) {
   HIPCHK(hipSetDevice(mb->device));
+  {
+    int rcs = match_settle(mb);  // (no wave steps the stream, no learn is still noted)
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(mb->stream));
   const uint8_t* bank = mb->banks + (size_t)stream * mb->dev.bank_bytes;
   HIPCHK(hipMemcpy(ms, bank + mb->dev.mstate_off, GMX_MATCH_MAX_MODELS * sizeof(GmxMatchModelState),
@@ -881,6 +1018,11 @@ extern "C" int gmx_match_copy(gmx_match* dst, int dst_stream, gmx_match* src, in
       return GMX_ERR_INVALID;
   if (dst == src && dst_stream == src_stream) return GMX_OK;
   HIPCHK(hipSetDevice(src->device));
+  {
+    int rcs = match_settle(src);
+    if (!rcs && dst != src) rcs = match_settle(dst);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(src->stream));
   GmxMatchStreamState ss;
   HIPCHK(hipMemcpy(&ss, src->banks + (size_t)src_stream * src->dev.bank_bytes + src->dev.sstate_off, sizeof ss,

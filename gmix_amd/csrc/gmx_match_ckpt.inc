@@ -77,6 +77,10 @@ extern "C" int gmx_match_group_export(gmx_match* mb, int first, int count, void*
   const GmxMatchDev& d = mb->dev;
   const size_t K = (size_t)d.k, C = mb->chunks.size(), n = (size_t)count;
   HIPCHK(hipSetDevice(mb->device));
+  {
+    int rcs = match_settle(mb);  // (hosted streams: no wave steps them, no learn is still noted; not counted)
+    if (rcs) return rcs;
+  }
   GCK(hipStreamSynchronize(mb->stream));  // (drains the bank's stream, as match_read_states does for gmx_match_export)
   int rc = match_ckpt_ready(mb);
   if (rc) return rc;
@@ -212,6 +216,10 @@ extern "C" int gmx_match_group_import(gmx_match* mb, int first, int count, const
   }
   const size_t bytes = long_off[count] - long_off[0], img_bytes = round_up64(bytes, 16);
   HIPCHK(hipSetDevice(mb->device));
+  {
+    int rcs = match_settle(mb);
+    if (rcs) return rcs;
+  }
   GCK(hipStreamSynchronize(mb->stream));  // (drains the bank's stream, as gmx_match_import does)
   int rc = match_ckpt_ready(mb);
   if (rc) return rc;

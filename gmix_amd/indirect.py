@@ -34,6 +34,7 @@ class IndirectGroup:
         check(self.L.gmx_indirect_create(C.byref(h), descs, self.K, _vp(ns), _vp(rm), self.S, device),
               "gmx_indirect_create")
         self.h = h
+        self.match = None
 
     def set_cu_mask(self, words=None):
         """Compute units this bank's kernels may use: 32-bit words, bit i = CU i (None: all)."""
@@ -90,6 +91,39 @@ class IndirectGroup:
         check(self.L.gmx_chain_forward(self.h, group.h, stream, _vp(c), int(bit_context), _vp(pr), _vp(ac), len(ac),
                                        _vp(mc), C.byref(p), _vp(out), _vp(pred), _vp(act)), "gmx_chain_forward")
         return p.value, out, pred, act
+
+    def attach_match(self, mg, cols=()):
+        """gmx_indirect_attach_match: the streams of the MatchGroup `mg` ride in this bank's per-bit session waves;
+        `cols` = the mixers' gate-context columns that receive longest_match.  mg=None detaches."""
+        c = np.ascontiguousarray(cols, np.int32)
+        check(self.L.gmx_indirect_attach_match(self.h, mg.h if mg is not None else None,
+                                               c.ctypes.data_as(C.POINTER(C.c_int32)), len(c)),
+              "gmx_indirect_attach_match")
+        self.match = mg  # (the C objects register with each other: either may be closed first)
+
+    def chain_forward_match(self, group, contexts, match_contexts, bit_context, predictions, active, mixer_contexts,
+                            stream=0):
+        """gmx_chain_forward_match: the attached Match bank's Predict, this bank's and the mixers' as one call.
+        Returns what chain_forward returns plus (match predictions[K], match active[K], longest_match)."""
+        mg = self.match
+        c = np.ascontiguousarray(contexts, np.uint32)
+        mx = np.ascontiguousarray(match_contexts, np.uint32)
+        pr = np.ascontiguousarray(predictions, np.float32)
+        ac = np.ascontiguousarray(active, np.int32)
+        mc = np.ascontiguousarray(mixer_contexts, np.uint32)
+        assert c.shape == (self.K,) and pr.shape == (group.topo.n_inputs,) and mc.shape == (group.topo.n_mixers,)
+        assert mg is not None and mx.shape == (mg.K,)
+        p = C.c_float()
+        out = np.zeros(group.topo.n_mixers, np.float32)
+        pred = np.zeros(2 * self.K, np.float32)
+        act = np.zeros(2 * self.K, np.uint8)
+        mpred = np.zeros(mg.K, np.float32)
+        mact = np.zeros(mg.K, np.uint8)
+        lm = C.c_uint32(0)
+        check(self.L.gmx_chain_forward_match(self.h, group.h, stream, _vp(c), _vp(mx), int(bit_context), _vp(pr),
+                                             _vp(ac), len(ac), _vp(mc), C.byref(p), _vp(out), _vp(pred), _vp(act),
+                                             _vp(mpred), _vp(mact), C.byref(lm)), "gmx_chain_forward_match")
+        return p.value, out, pred, act, mpred, mact, lm.value
 
     def run(self, batch, n_bits=None, learn=True, into=None, timed=False):
         n_bits = batch.max_bits if n_bits is None else n_bits

@@ -640,6 +640,35 @@ int gmx_chainstep_wait(gmx_chainstep* cs);
 int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, const int32_t* ctx_columns, int n_ctx_columns);
 uint32_t* gmx_chainstep_match_contexts(gmx_chainstep* cs);   /* pinned host [S][K_match]; NULL before attach */
 
+/* ==== The Match models in the per-bit session chain ================================================
+ * gmx_indirect_attach_match: the bank's streams ride in ib's per-bit session waves (lanes 56..63 of the one wave a
+ * stream's Indirect models have; a process has no hardware queue for a fourth persistent kernel).  ctx_columns: the
+ * mixers' gate-context columns that receive longest_match.  mb == NULL detaches.  GMX_ERR_INVALID: more than 56
+ * Indirect models, another stream count or device, a column < 0, more than 8 columns, a Match slot that is also an
+ * Indirect model's (a column beyond the mixer group's is refused by the call below, which knows the group).
+ * GMX_ERR_STATE: mb is attached to a gmx_chainstep, or to another Indirect bank.  Attaching again replaces the
+ * columns.  The two objects register with each other: destroying either one detaches first.
+ *
+ * gmx_chain_forward_match: gmx_match_forward, then gmx_chain_forward with the Match models' slot values and active
+ * flags merged into predictions / active_models and contexts[ctx_columns[c]] = longest_match -- as ONE command and
+ * one wait when gmx_chain_forward's own conditions for its one-round-trip path hold (same device, both banks on
+ * sessions, mixers of the stock shape), as those calls one after the other otherwise: the same floats and the same
+ * state in every bank either way.  Whatever the caller passes in the Match slots, the Indirect slots and those
+ * columns is ignored.  Learn stays gmx_indirect_learn, gmx_bank_learn and gmx_match_learn; on a stream whose newest
+ * Match forward went through a session wave gmx_match_learn only notes the bit, which travels with the stream's next
+ * chained forward (every other gmx_match_* call that reads or writes the bank first stops ib's sessions and runs a
+ * noted learn through the launch path; a learn that could take the history past history_capacity is refused by
+ * gmx_match_learn itself, GMX_ERR_INVALID, and not noted).  Before either bank moves: GMX_ERR_INVALID for a column >=
+ * the group's M or a Match slot >= its n; GMX_ERR_STATE for a second forward of the stream without a learn, and when
+ * no bank is attached. */
+int gmx_indirect_attach_match(gmx_indirect* ib, gmx_match* mb, const int32_t* ctx_columns, int n_ctx_columns);
+int gmx_chain_forward_match(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
+                            const uint32_t* match_contexts, uint32_t bit_context, const float* predictions,
+                            const int32_t* active_models, int n_active, const uint32_t* contexts, float* p_final,
+                            float* out_all, float* ind_predictions, uint8_t* ind_active,
+                            float* match_predictions /* [K] */, uint8_t* match_active /* [K] */,
+                            uint32_t* longest_match);
+
 /* ==== Compute-unit shares ======================================================================
  * A bank's kernels normally spread over the whole chip.  Kernels of DIFFERENT banks that cannot share
  * a SIMD -- a mixer wave of the stock shape owns all 512 registers of its SIMD, an LSTM workgroup
