@@ -7,7 +7,8 @@ from .bank import Batch, ChainStep, Lockstep, MixerGroup, Topology, device_count
 from .indirect import IndirectBatch, IndirectGroup
 from .lstm import LstmBatch, LstmGroup
 from .match import MatchBatch, MatchGroup
+from .ctx import CtxBatch, CtxGroup
 
 __all__ = ["topology", "ABI_SYMBOLS", "LIB_PATH", "GmxError", "build", "Batch", "MixerGroup",
            "Lockstep", "ChainStep", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch",
-           "MatchGroup", "MatchBatch"]
+           "MatchGroup", "MatchBatch", "CtxGroup", "CtxBatch"]

@@ -32,6 +32,24 @@ class MatchDesc(C.Structure):
     _fields_ = [("table_size", C.c_uint32), ("limit", C.c_int32), ("slot", C.c_int32)]
 
 
+class CtxDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("num_bits", C.c_int32), ("n_bytes", C.c_int32),
+                ("outer_order", C.c_int32), ("inner_order", C.c_int32), ("table_size", C.c_uint32),
+                ("bytes_to_use", C.c_uint8 * 8), ("map", C.c_uint8 * 256)]
+
+
+class CtxTargets(C.Structure):
+    _fields_ = [("mixers", C.c_void_p), ("mixer_route", C.POINTER(C.c_int32)), ("n_mixer_route", C.c_int32),
+                ("indirect", C.c_void_p), ("ind_route", C.POINTER(C.c_int32)), ("n_ind_route", C.c_int32),
+                ("match", C.c_void_p), ("match_route", C.POINTER(C.c_int32)), ("n_match_route", C.c_int32)]
+
+
+class CtxBlackboard(C.Structure):
+    _fields_ = [("recent_bits", C.c_int32), ("new_bit", C.c_int32), ("last_byte", C.c_uint32),
+                ("rotating_history_pos", C.c_uint32), ("first_prediction", C.c_int32),
+                ("recent_bytes", C.c_uint32 * 10), ("values", C.c_uint32 * 64), ("rotating_history", C.c_uint8 * 1000)]
+
+
 class TopologyStruct(C.Structure):
     _fields_ = [("n_inputs", C.c_int32), ("n_skip", C.c_int32), ("skip_index", C.POINTER(C.c_int32)),
                 ("n_mixers", C.c_int32), ("mixers", C.POINTER(MixerDesc))]
@@ -196,6 +214,35 @@ def lib():
     L.gmx_match_group_export.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.gmx_match_group_import.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_size_t), vp]
     L.gmx_match_memory_usage.argtypes = [vp, i32, C.POINTER(u64)]
+    L.gmx_ctx_create.argtypes = [C.POINTER(vp), C.POINTER(CtxDesc), i32, i32, i32]
+    L.gmx_ctx_destroy.argtypes = [vp]
+    L.gmx_ctx_destroy.restype = None
+    for f in (L.gmx_ctx_n_streams, L.gmx_ctx_n_vars, L.gmx_ctx_reset, L.gmx_ctx_sync):
+        f.argtypes = [vp]
+    L.gmx_ctx_bank_bytes.argtypes = [vp]
+    L.gmx_ctx_bank_bytes.restype = u64
+    L.gmx_ctx_set_cu_mask.argtypes = [vp, C.POINTER(u32), i32]
+    L.gmx_ctx_batch_create.argtypes = [C.POINTER(vp), vp, u64, C.c_uint]
+    L.gmx_ctx_batch_destroy.argtypes = [vp]
+    L.gmx_ctx_batch_destroy.restype = None
+    L.gmx_ctx_batch_max_bits.argtypes = [vp]
+    L.gmx_ctx_batch_max_bits.restype = u64
+    for name in ("bits", "values"):
+        f = getattr(L, "gmx_ctx_batch_" + name)
+        f.argtypes = [vp]
+        f.restype = vp
+    L.gmx_ctx_batch_upload.argtypes = [vp, u64]
+    L.gmx_ctx_batch_download.argtypes = [vp, u64]
+    L.gmx_ctx_batch_wait.argtypes = [vp]
+    L.gmx_ctx_run.argtypes = [vp, vp, u64, C.POINTER(CtxTargets), C.POINTER(C.c_float)]
+    L.gmx_ctx_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gmx_ctx_run_ragged.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(CtxTargets)]
+    L.gmx_ctx_blackboard_get.argtypes = [vp, i32, C.POINTER(CtxBlackboard)]
+    L.gmx_ctx_blackboard_set.argtypes = [vp, i32, C.POINTER(CtxBlackboard)]
+    L.gmx_ctx_export.argtypes = [vp, i32, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.gmx_ctx_import.argtypes = [vp, i32, vp, C.c_size_t]
+    L.gmx_ctx_copy.argtypes = [vp, i32, vp, i32]
+    L.gmx_ctx_memory_usage.argtypes = [vp, i32, C.POINTER(u64)]
     L.gmx_lockstep_create.argtypes = [C.POINTER(vp), vp, C.c_uint]
     L.gmx_lockstep_destroy.argtypes = [vp]
     L.gmx_lockstep_destroy.restype = None
@@ -271,4 +318,9 @@ ABI_SYMBOLS = [
     "gmx_match_batch_download", "gmx_match_batch_wait", "gmx_match_run", "gmx_match_run_ragged", "gmx_match_forward",
     "gmx_match_learn", "gmx_match_slots_get", "gmx_match_slots_set", "gmx_match_history_size", "gmx_match_export",
     "gmx_match_import", "gmx_match_copy", "gmx_match_memory_usage", "gmx_match_group_export", "gmx_match_group_import",
+    "gmx_ctx_create", "gmx_ctx_destroy", "gmx_ctx_n_streams", "gmx_ctx_n_vars", "gmx_ctx_bank_bytes", "gmx_ctx_reset",
+    "gmx_ctx_sync", "gmx_ctx_set_cu_mask", "gmx_ctx_batch_create", "gmx_ctx_batch_destroy", "gmx_ctx_batch_max_bits",
+    "gmx_ctx_batch_bits", "gmx_ctx_batch_values", "gmx_ctx_batch_upload", "gmx_ctx_batch_download",
+    "gmx_ctx_batch_wait", "gmx_ctx_run", "gmx_ctx_run_ragged", "gmx_ctx_blackboard_get", "gmx_ctx_blackboard_set",
+    "gmx_ctx_export", "gmx_ctx_import", "gmx_ctx_copy", "gmx_ctx_memory_usage", "gmx_ctx_last_kernel_ms",
 ]

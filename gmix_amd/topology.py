@@ -95,3 +95,47 @@ def stock_match():
 def stock_longest_match_columns():
     """Gate-context columns of the stock mixers that read ShortTermMemory::longest_match (6 and 30)."""
     return [i for i, c in enumerate(stock_context_names()) if c == "longest_match"]
+
+
+# The context variables of the reference's Predictor (predictor.cpp:54-76 AddIntervalContexts, :78-185 the SkipContext
+# objects of AddIndirect and AddSkip, :210-249 the IndirectHash objects of AddDoubleIndirect) and the context fields of
+# BasicContexts: (name, kind, parameters) as gmix_amd.ctx.CtxGroup takes them.
+STOCK_INTERVALS = [(f"interval_{d}_{n}", d, n) for d, bits in ((16, (4, 8, 12)), (32, (3, 6, 12)), (64, (4, 8, 12)))
+                   for n in bits]
+STOCK_LAST_N = [("last_two_bytes_hash", 2), ("last_three_bytes_hash", 3), ("last_four_bytes_hash", 4),
+                ("last_five_bytes_hash", 5), ("last_six_bytes_hash", 6)]
+STOCK_INDIRECT_HASH = [("indirect_1_8_1", 1, 1 << 8, 1), ("indirect_1_8_2", 1, 1 << 8, 2),
+                       ("indirect_1_8_3", 1, 1 << 8, 3), ("indirect_2_16_1", 2, 1 << 16, 1),
+                       ("indirect_2_16_2", 2, 1 << 16, 2), ("indirect_2_16_3", 2, 1 << 16, 3),
+                       ("indirect_3_24_1", 3, 1 << 24, 1), ("indirect_4_24_2", 4, 1 << 24, 2),
+                       ("indirect_4_24_3", 4, 1 << 24, 3)]
+# written by other banks: gmx_match_run and gmx_lstm_feed
+STOCK_FOREIGN_CONTEXTS = ("longest_match", "lstm_prediction_context")
+
+
+def stock_context_descs():
+    """[(name, kind, params)] of the 52 stock context variables."""
+    out = [(name, "interval", dict(map=[i // d for i in range(256)], num_bits=n)) for name, d, n in STOCK_INTERVALS]
+    out += [(name, "skip", dict(bytes_to_use=list(range(n)))) for name, n in STOCK_LAST_N]
+    out += [(c, "skip", dict(bytes_to_use=[int(x) for x in c.split("_")[1:]]))
+            for c, _, _ in STOCK_INDIRECT if c.startswith("skip_")]
+    out += [(name, "indirect_hash", dict(outer_order=o, table_size=t, inner_order=i))
+            for name, o, t, i in STOCK_INDIRECT_HASH]
+    out += [("last_byte", "recent_byte", dict(index=0))]
+    out += [(f"recent_bytes[{i}]", "recent_byte", dict(index=i)) for i in range(1, 10)]
+    out += [("bit_context", "bit_context", {}), ("last_byte_plus_recent", "byte_plus_recent", dict(index=0)),
+            ("second_last_plus_recent", "byte_plus_recent", dict(index=1)), ("always_zero", "zero", {})]
+    return out
+
+
+def stock_contexts():
+    """(descs, mixer_route, ind_route, match_route): the stock variables and, derived by name from STOCK_LAYER0/1/FINAL,
+    STOCK_INDIRECT and STOCK_MATCH, the variable every context column of the three record batches receives; -1 for
+    longest_match and lstm_prediction_context, which other banks write."""
+    descs = stock_context_descs()
+    index = {name: i for i, (name, _, _) in enumerate(descs)}
+
+    def route(names):
+        return [-1 if n in STOCK_FOREIGN_CONTEXTS else index[n] for n in names]
+    return (descs, route(stock_context_names()), route([c for c, _, _ in STOCK_INDIRECT]),
+            route([c for c, _ in STOCK_MATCH]))

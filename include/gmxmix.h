@@ -682,6 +682,136 @@ int gmx_group_set_cu_mask(gmx_group* g, const uint32_t* mask, int n_words);
 int gmx_indirect_set_cu_mask(gmx_indirect* ib, const uint32_t* mask, int n_words);
 int gmx_lstm_set_cu_mask(gmx_lstm* l, const uint32_t* mask, int n_words);
 
+/* ==== Context variables ========================================================================
+ * The context values the models and mixers are gated by, computed on the device from the coded bits alone: the
+ * context fields of BasicContexts (basic-contexts.cpp:5-40), IntervalContext (interval-context.cpp:3-23), SkipContext
+ * (skip-context.cpp:9-18) and IndirectHash (indirect-hash.cpp:7-54) over ShortTermMemory's byte-level blackboard
+ * (recent_bits, last_byte, rotating_history, recent_bytes), for S streams on one device.  A bank is described by an
+ * ordered list of V <= 64 variables; a run writes, for every bit, the values the variables have at Predict of that
+ * bit -- into a debugging array of the bank's own batch and into the context columns of up to three record batches
+ * of the other banks.  The adapter (dropin/) does not use these banks yet. */
+typedef enum gmx_ctx_kind {
+  GMX_CTX_ZERO = 0,             /* always_zero */
+  GMX_CTX_BIT_CONTEXT = 1,      /* bit_context = recent_bits - 1 */
+  GMX_CTX_RECENT_BYTE = 2,      /* recent_bytes[index]; index 0 is last_byte.  index 0..9 */
+  GMX_CTX_BYTE_PLUS_RECENT = 3, /* (recent_bytes[index] << 8) + bit_context.  index 0..9 */
+  GMX_CTX_INTERVAL = 4,         /* IntervalContext(map, num_bits): num_bits 1..31, shift_ derived from map */
+  GMX_CTX_SKIP = 5,             /* SkipContext(bytes_to_use): n_bytes 1..8 entries, each 0..15 */
+  GMX_CTX_INDIRECT_HASH = 6     /* IndirectHash(outer_order, table_size, inner_order): orders 1..4 (the reference
+                                 * shifts an int by 8 * (order - 1): larger orders are undefined there), table_size >= 1,
+                                 * any size; at most 16 such variables per bank, each with a dense u32 table per
+                                 * stream in device memory */
+} gmx_ctx_kind;
+
+typedef struct gmx_ctx_desc {
+  int32_t kind;
+  int32_t index;
+  int32_t num_bits;
+  int32_t n_bytes;
+  int32_t outer_order, inner_order;
+  uint32_t table_size;
+  uint8_t bytes_to_use[8];
+  uint8_t map[256];
+} gmx_ctx_desc;
+
+typedef struct gmx_ctx gmx_ctx;
+typedef struct gmx_ctx_batch gmx_ctx_batch;
+
+/* GMX_ERR_INVALID for bad arguments (V outside 1..64, more than 16 hash variables, a parameter outside the ranges
+ * above, n_streams < 1), GMX_ERR_NO_DEVICE without a GPU: there is no CPU fallback.  Constructed state: every table
+ * zero, the blackboard as ShortTermMemory's constructor leaves it, first_prediction_ set. */
+int gmx_ctx_create(gmx_ctx** out, const gmx_ctx_desc* descs, int n_vars, int n_streams, int device);
+void gmx_ctx_destroy(gmx_ctx* cb);
+int gmx_ctx_n_streams(const gmx_ctx* cb);
+int gmx_ctx_n_vars(const gmx_ctx* cb);
+uint64_t gmx_ctx_bank_bytes(const gmx_ctx* cb);  /* device bytes per stream (stock: 201 MB, the nine hash tables) */
+int gmx_ctx_reset(gmx_ctx* cb);
+int gmx_ctx_sync(gmx_ctx* cb);
+int gmx_ctx_set_cu_mask(gmx_ctx* cb, const uint32_t* mask, int n_words);  /* cf. gmx_group_set_cu_mask */
+
+/* The bank's own batch: the coded bits of up to max_bits (<= 2^30) bits per stream, the only input.
+ *   bits   [S][max_bits]      pinned host, caller fills
+ *   values [S][max_bits][V]   pinned host, filled by download: every variable at Predict of every bit.  Only with
+ *                             GMX_CTX_BATCH_VALUES; otherwise NULL, and no device array of that size exists.
+ * Transfers run on the bank's own stream, like a Match batch's. */
+#define GMX_CTX_BATCH_VALUES 1u
+int gmx_ctx_batch_create(gmx_ctx_batch** out, gmx_ctx* cb, uint64_t max_bits, unsigned flags);
+void gmx_ctx_batch_destroy(gmx_ctx_batch* b);
+uint64_t gmx_ctx_batch_max_bits(const gmx_ctx_batch* b);
+uint8_t* gmx_ctx_batch_bits(gmx_ctx_batch* b);
+const uint32_t* gmx_ctx_batch_values(gmx_ctx_batch* b);
+int gmx_ctx_batch_upload(gmx_ctx_batch* b, uint64_t n_bits);
+int gmx_ctx_batch_download(gmx_ctx_batch* b, uint64_t n_bits);
+int gmx_ctx_batch_wait(gmx_ctx_batch* b);
+
+/* Where a run writes besides the batch's values.  Every member is nullable.  A route has one entry per context
+ * column of the target's records (mixers: the group's M gate contexts; Indirect / Match: the bank's K models): the
+ * index of the variable the column receives, or -1 to leave the column alone (longest_match is gmx_match_run's,
+ * lstm_prediction_context gmx_lstm_feed's).  For the Indirect and the Match batch the run also writes the
+ * bit_contexts and bits records; for the mixer batch only the routed columns (gmx_indirect_run copies the bits). */
+typedef struct gmx_ctx_targets {
+  gmx_batch* mixers;
+  const int32_t* mixer_route;
+  int32_t n_mixer_route;        /* == M */
+  gmx_ind_batch* indirect;
+  const int32_t* ind_route;
+  int32_t n_ind_route;          /* == K of the Indirect bank */
+  gmx_match_batch* match;
+  const int32_t* match_route;
+  int32_t n_match_route;        /* == K of the Match bank */
+} gmx_ctx_targets;
+
+/* Bits [0, n_bits) of every stream.  Record t holds the values at Predict of bit t, in Predictor's order
+ * (BasicContexts first): byte-level variables move only at records where recent_bits == 1, and the very first Predict
+ * of a stream is such a record (first_prediction_: BasicContexts returns early, every SkipContext, IntervalContext and
+ * IndirectHash fires with last_byte 0 and an all-zero history).  A run may begin and end anywhere in a byte; the
+ * stream's state in device memory is complete after every launch.  Writes into a target are ordered like
+ * gmx_match_run's `into`: after what was queued on the target's owner before the call and after the target batch's
+ * own upload, before what is queued on the owner afterwards.  Everything is validated before anything is queued:
+ * GMX_ERR_INVALID for a target with another stream count or device, n_bits beyond a batch's max_bits, a route of the
+ * wrong length (or longer than 128) or with an entry outside [-1, V). */
+int gmx_ctx_run(gmx_ctx* cb, gmx_ctx_batch* b, uint64_t n_bits, const gmx_ctx_targets* targets, float* kernel_ms);
+/* Of the newest gmx_ctx_run that was given kernel_ms: what the chain, the expand and the commit kernel took (ms[3];
+ * their sum is that run's kernel_ms).  For scripts/bench_ctx.py. */
+int gmx_ctx_last_kernel_ms(const gmx_ctx* cb, float* ms /* [3] */);
+/* ... stream s runs bits [0, n_bits[s]), 0 = it sits the launch out.  One launch sequence whatever the lengths. */
+int gmx_ctx_run_ragged(gmx_ctx* cb, gmx_ctx_batch* b, const uint64_t* n_bits /* [S] */,
+                       const gmx_ctx_targets* targets);
+
+/* What ShortTermMemory carries of this state (plus BasicContexts::first_prediction_ and the V current values), as
+ * of the stream's newest Predict; new_bit is the bit coded since.  set refuses (GMX_ERR_INVALID) a blackboard whose
+ * last_byte / recent_bytes are not what rotating_history holds at rotating_history_pos, recent_bits outside 1..255,
+ * and first_prediction with recent_bits != 1.  A checkpoint taken inside a byte and restored into any stream of a
+ * bank of the same variables continues identically (with gmx_ctx_import for the hash tables). */
+typedef struct gmx_ctx_blackboard {
+  int32_t recent_bits;
+  int32_t new_bit;
+  uint32_t last_byte;
+  uint32_t rotating_history_pos;
+  int32_t first_prediction;
+  uint32_t recent_bytes[10];
+  uint32_t values[64];
+  uint8_t rotating_history[1000];
+} gmx_ctx_blackboard;
+int gmx_ctx_blackboard_get(gmx_ctx* cb, int stream, gmx_ctx_blackboard* out);
+int gmx_ctx_blackboard_set(gmx_ctx* cb, int stream, const gmx_ctx_blackboard* in);
+
+/* The concatenation, in descriptor order, of IndirectHash::WriteToDisk of the H hash variables, byte for byte
+ * (indirect-hash.cpp:33-54): u32 count of non-zero entries; {u32 key, u32 value} in ascending key order when count <
+ * table_size / 2 (integer division), else the whole table; u64 outer_context_, u32 outer_hash_.  offsets (nullable,
+ * [H + 1]) receives where each variable's section begins.  buf == NULL: *bytes and offsets only.  Non-zero entries are
+ * counted and packed on the device.  import validates everything before the bank is touched -- lengths, the branch
+ * against the count, strictly ascending keys below the table size, no zero value in a sparse record, the count of a
+ * dense one -- returns GMX_ERR_FORMAT otherwise, and leaves the blackboard alone. */
+int gmx_ctx_export(gmx_ctx* cb, int stream, void* buf, size_t* bytes, size_t* offsets /* [H + 1] */);
+int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t bytes);
+/* Tables, hash states and blackboard of one stream into another, between banks of the same variables on the same
+ * device.  (No entry point of this library locks: as everywhere, a handle is used by one thread at a time.) */
+int gmx_ctx_copy(gmx_ctx* dst, int dst_stream, gmx_ctx* src, int src_stream);
+/* GetMemoryUsage of the variable's object: IndirectHash 36 + 4 table_size (indirect-hash.cpp:83-89), IntervalContext
+ * 256 * 4 + 8 + 4, SkipContext 4 n_bytes + 4; 0 for the fields of BasicContexts, which have no object of their own. */
+int gmx_ctx_memory_usage(gmx_ctx* cb, int var, uint64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif
