@@ -44,6 +44,12 @@ class CtxTargets(C.Structure):
                 ("match", C.c_void_p), ("match_route", C.POINTER(C.c_int32)), ("n_match_route", C.c_int32)]
 
 
+class CtxStepRoutes(C.Structure):
+    _fields_ = [("mixer_route", C.POINTER(C.c_int32)), ("n_mixer_route", C.c_int32),
+                ("ind_route", C.POINTER(C.c_int32)), ("n_ind_route", C.c_int32),
+                ("match_route", C.POINTER(C.c_int32)), ("n_match_route", C.c_int32)]
+
+
 class CtxBlackboard(C.Structure):
     _fields_ = [("recent_bits", C.c_int32), ("new_bit", C.c_int32), ("last_byte", C.c_uint32),
                 ("rotating_history_pos", C.c_uint32), ("first_prediction", C.c_int32),
@@ -243,6 +249,10 @@ def lib():
     L.gmx_ctx_import.argtypes = [vp, i32, vp, C.c_size_t]
     L.gmx_ctx_copy.argtypes = [vp, i32, vp, i32]
     L.gmx_ctx_memory_usage.argtypes = [vp, i32, C.POINTER(u64)]
+    L.gmx_chainstep_attach_ctx.argtypes = [vp, vp, C.POINTER(CtxStepRoutes)]
+    L.gmx_chainstep_commit_bytes.argtypes = [vp]
+    L.gmx_chainstep_commit_bytes.restype = u64
+    L.gmx_chainstep_timed_step.argtypes = [vp, C.POINTER(C.c_float)]
     L.gmx_lockstep_create.argtypes = [C.POINTER(vp), vp, C.c_uint]
     L.gmx_lockstep_destroy.argtypes = [vp]
     L.gmx_lockstep_destroy.restype = None
@@ -323,4 +333,5 @@ ABI_SYMBOLS = [
     "gmx_ctx_batch_bits", "gmx_ctx_batch_values", "gmx_ctx_batch_upload", "gmx_ctx_batch_download",
     "gmx_ctx_batch_wait", "gmx_ctx_run", "gmx_ctx_run_ragged", "gmx_ctx_blackboard_get", "gmx_ctx_blackboard_set",
     "gmx_ctx_export", "gmx_ctx_import", "gmx_ctx_copy", "gmx_ctx_memory_usage", "gmx_ctx_last_kernel_ms",
+    "gmx_chainstep_attach_ctx", "gmx_chainstep_commit_bytes", "gmx_chainstep_timed_step",
 ]

@@ -417,6 +417,27 @@ class ChainStep:
         if self.bit_contexts is None:
             self.bit_contexts = self._view("bit_contexts", np.uint32, (self.g.S,))
 
+    def attach_ctx(self, group, mixer_route, ind_route=None, match_route=None):
+        """The context variables of `group` (a CtxGroup of as many streams) step on the device from now on
+        (gmx_chainstep_attach_ctx): once, before the first step, after attach_match.  A route names a variable per
+        column, -1 leaves the column to the caller.  Afterwards the routed columns of `contexts`, `ind_contexts` and
+        `match_contexts`, and `bit_contexts`, are ignored."""
+        r = _lib.CtxStepRoutes()
+        keep = []
+        for name, route in (("mixer", mixer_route), ("ind", ind_route), ("match", match_route)):
+            if route is None:
+                continue
+            a = np.ascontiguousarray(route, np.int32)
+            keep.append(a)
+            setattr(r, name + "_route", a.ctypes.data_as(C.POINTER(C.c_int32)))
+            setattr(r, "n_" + name + "_route", len(a))
+        check(self.L.gmx_chainstep_attach_ctx(self.h, group.h, C.byref(r)), "gmx_chainstep_attach_ctx")
+
+    @property
+    def commit_bytes(self):
+        """Bytes of records per stream a commit moves (gmx_chainstep_commit_bytes)."""
+        return int(self.L.gmx_chainstep_commit_bytes(self.h))
+
     def set_active(self, stream, active):
         """active[N] flags -> the stream's mask words."""
         padded = np.zeros(self.mask_words * 32, np.uint8)
@@ -430,6 +451,12 @@ class ChainStep:
 
     def step(self):
         check(self.L.gmx_chainstep_step(self.h), "gmx_chainstep_step")
+
+    def timed_step(self):
+        """step() with HIP events around the step's graph -> device milliseconds (gmx_chainstep_timed_step)."""
+        ms = C.c_float(0)
+        check(self.L.gmx_chainstep_timed_step(self.h, C.byref(ms)), "gmx_chainstep_timed_step")
+        return ms.value
 
     def launch(self):
         """step() in two halves: queued when this returns ..."""

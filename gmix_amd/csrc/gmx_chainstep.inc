@@ -19,6 +19,10 @@
 // Then 89 of the 90 inputs and the gate contexts of mixers 6 and 30 never leave the device; the host supplies the bit
 // context per predict and the models' context words per byte-opening predict.
 //
+// With a context bank attached (gmx_chainstep_attach_ctx) the step begins with gmx_ctx_step_kernel (gmx_ctx_step.h): the
+// bank takes the stream's bit and writes the routed context columns, the Match models' context words and the bit context
+// of this step's device copy, so the host supplies none of them and the arrays it owns no column of leave the slices.
+//
 // as ONE hipGraph of kernels only.  No copy node: a graph's small memcpy nodes cost 9-11 us EACH on this part
 // (scripts/trace_chainstep.sh: three uploads and a download were 35 of a step's 53 us).
 //
@@ -69,6 +73,13 @@ struct gmx_chainstep {
   uint32_t* mctx = nullptr;        // host view [S][K_match]: the Match models' context words (room for 8 a stream)
   std::vector<uint32_t> m_bc;      // bit_context of the stream's outstanding Predict (does its Learn complete a byte?)
   std::vector<uint8_t> m_seen;     // the stream has predicted through this object (its first Predict reads mctx)
+  gmx_ctx* cb = nullptr;           // gmx_chainstep_attach_ctx: the context variables step on the device too
+  bool cb_gone = false;            // ... and that bank has been destroyed
+  bool broken = false;             // an attach failed while it captured the graphs anew: there is nothing to launch
+  GmxCtxTarget c_tg[3] = {};       // its routes into the mixers', the Indirect models' and the Match models' words
+  std::vector<uint8_t> c_pos;      // where in its byte the stream's next Predict falls (from the board at attach)
+  hipEvent_t t_ev[2] = {};         // gmx_chainstep_timed_step: around the step's graph, on the group's stream
+  bool timed = false, timed_ok = false;
   int S = 0, lstm_slot = -1, mixer_ctx_col = -1, ind_ctx_col = -1;
   // h_in: ONE pinned host block [control words | records], uploaded by the step's first kernel into d_in[parity];
   // h_bd: what a byte-opening step adds (PPM distributions, the bytes just completed, the LSTM's counts) -> d_bd;
@@ -126,8 +137,27 @@ static void chainstep_match_gone(gmx_chainstep* cs) {
   cs->mb_gone = true;
 }
 
+static void chainstep_ctx_gone(gmx_chainstep* cs) {
+  if (cs->g) {
+    (void)hipSetDevice(cs->g->device);
+    if (cs->g->stream) (void)hipStreamSynchronize(cs->g->stream);  // (a step in flight still writes the bank)
+  }
+  cs->cb = nullptr;
+  cs->cb_gone = true;
+}
+
+// What a gmx_ctx_* call on an attached bank waits for: the steps run on the group's stream.
+static int chainstep_settle(gmx_chainstep* cs) {
+  if (!cs->g || !cs->g->stream) return GMX_OK;
+  HIPCHK(hipSetDevice(cs->g->device));
+  if (hipStreamQuery(cs->g->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(cs->g->stream));
+  (void)hipGetLastError();
+  return GMX_OK;
+}
+
 extern "C" void gmx_chainstep_destroy(gmx_chainstep* cs) {
   if (!cs) return;
+  if (cs->cb) cs->cb->chainstep = nullptr;
   if (cs->mb) {
     auto& v = cs->mb->chainsteps;
     v.erase(std::remove(v.begin(), v.end(), cs), v.end());
@@ -141,6 +171,8 @@ extern "C" void gmx_chainstep_destroy(gmx_chainstep* cs) {
       if (cs->exec[p][o]) (void)hipGraphExecDestroy(cs->exec[p][o]);
       if (cs->graph[p][o]) (void)hipGraphDestroy(cs->graph[p][o]);
     }
+  for (hipEvent_t ev : cs->t_ev)
+    if (ev) (void)hipEventDestroy(ev);
   void* hv[] = {cs->h_in, cs->h_bd, cs->h_out, cs->adam_host};
   for (void* q : hv)
     if (q) (void)hipHostFree(q);
@@ -164,6 +196,30 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
   up.src = cs->h_in_dev;
   up.dst = cs->d_in[par];
   if (cs->bar) up.n = 0;  // the host has put them there
+  if (cs->cb) {
+    // the context bank's bit: behind the step's words and in front of every consumer of the records it writes.  Where
+    // the device fetches the step's inputs the fetch is a node of its own in front of it (inside the models' kernel it
+    // would overwrite what this node wrote)
+    if (up.n > 0) {
+      e = gmx_launch_step_upload(&up, cs->S, st);
+      if (e != hipSuccess) return e;
+      up.n = 0;
+    }
+    GmxCtxStepArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.banks = cs->cb->banks;
+    ca.bits = (const uint8_t*)cur(cs->bits);
+    ca.what = (const uint8_t*)cur(cs->what_dev);
+    ca.bc = (cs->ib || cs->mb) ? (uint32_t*)cur(cs->ibc) : nullptr;
+    ca.n_streams = cs->S;
+    const void* const rec[3] = {cs->ctx, cs->ictx, cs->mctx};
+    for (int k = 0; k < 3; ++k) {
+      ca.tg[k] = cs->c_tg[k];
+      ca.tg[k].ctx = cs->c_tg[k].n_cols > 0 ? (uint32_t*)cur(rec[k]) : nullptr;
+    }
+    e = gmx_launch_ctx_step(cs->cb->dev_d, &ca, st);
+    if (e != hipSuccess) return e;
+  }
   const uint8_t* const bits_d = (const uint8_t*)cur(cs->bits);
   const uint8_t* const what_d = (const uint8_t*)cur(cs->what_dev);
   float* const pred_d = (float*)cur(cs->pred);
@@ -553,7 +609,8 @@ extern "C" uint32_t* gmx_chainstep_match_contexts(gmx_chainstep* cs) { return (c
 extern "C" int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, const int32_t* ctx_columns,
                                           int n_ctx_columns) {
   if (!cs || !cs->g || !mb) return GMX_ERR_INVALID;
-  if (cs->mb || cs->steps != 0 || cs->in_flight) return GMX_ERR_STATE;  // once, before the first step
+  if (cs->mb || cs->cb || cs->cb_gone || cs->steps != 0 || cs->in_flight)
+    return GMX_ERR_STATE;  // once, before the first step -- and before a context bank, whose routes name its columns
   if (mb->host) return GMX_ERR_STATE;  // (its streams ride in per-bit session waves: gmx_indirect_attach_match)
   gmx_group* g = cs->g;
   const GmxTopoDev& t = g->topo;
@@ -586,6 +643,117 @@ extern "C" int gmx_chainstep_attach_match(gmx_chainstep* cs, gmx_match* mb, cons
     return e == hipErrorOutOfMemory ? GMX_ERR_NOMEM : hip_fail(e, "gmx_chainstep_attach_match: capture");
   }
   return GMX_OK;
+}
+
+// Where in its byte every stream's next Predict falls: recent_bits, new_bit and first_prediction head the board, read
+// for all streams in one transfer.  At attach, and again before a step when a gmx_ctx_* call between the steps may have
+// moved a stream (gmx_ctx_run, _blackboard_set, _copy, _reset).  A stream whose Predict waits for its Learn keeps its
+// count: those calls refuse it, and its new_bit means nothing.
+static int cs_read_positions(gmx_chainstep* cs, gmx_ctx* cb) {
+  gmx_group* g = cs->g;
+  std::vector<uint32_t> head((size_t)cs->S * 3);
+  uint32_t* head_d = nullptr;
+  HIPCHK(hipMalloc((void**)&head_d, head.size() * 4));
+  hipError_t eh = gmx_launch_ctx_heads(cb->dev_d, cb->banks, cs->S, head_d, g->stream);
+  if (eh == hipSuccess) eh = hipMemcpyAsync(head.data(), head_d, head.size() * 4, hipMemcpyDeviceToHost, g->stream);
+  if (eh == hipSuccess) eh = hipStreamSynchronize(g->stream);
+  (void)hipFree(head_d);
+  HIPCHK(eh);
+  for (int s = 0; s < cs->S; ++s) {
+    if (cs->pending[s]) continue;
+    const uint32_t rb = head[3 * s], nb = head[3 * s + 1], fp = head[3 * s + 2];
+    const uint32_t p = fp ? rb : 2u * rb + (nb & 1u);
+    int n = 0;
+    for (uint32_t q = p; q > 1u; q >>= 1) ++n;  // the bits of the open byte the next Predict has in front of it
+    cs->c_pos[s] = (uint8_t)(n & 7);
+  }
+  return GMX_OK;
+}
+
+// The context variables of every stream step on the device from now on (gmx_ctx_step.h): the routed columns of
+// contexts / ind_contexts / match_contexts and bit_contexts are the bank's, whatever the staging arrays hold there.
+extern "C" int gmx_chainstep_attach_ctx(gmx_chainstep* cs, gmx_ctx* cb, const gmx_ctx_step_routes* routes) {
+  if (!cs || !cs->g || !cb || !routes) return GMX_ERR_INVALID;
+  if (cs->cb || cs->cb_gone || cs->steps != 0 || cs->in_flight) return GMX_ERR_STATE;  // once, before the first step
+  gmx_group* g = cs->g;
+  const GmxTopoDev& t = g->topo;
+  if (cb->S != cs->S || cb->device != g->device) return GMX_ERR_INVALID;
+  const int K = cs->ib ? cs->ib->dev.k : 0, KM = cs->mb ? cs->mb->dev.k : 0;
+  if (ctx_route_ok(cb, routes->mixer_route, routes->n_mixer_route, t.m)) return GMX_ERR_INVALID;
+  const bool has_ind = routes->ind_route || routes->n_ind_route, has_match = routes->match_route || routes->n_match_route;
+  if (has_ind != (K > 0) || has_match != (KM > 0)) return GMX_ERR_INVALID;  // NULL / 0 iff there is no such bank
+  if (has_ind && ctx_route_ok(cb, routes->ind_route, routes->n_ind_route, K)) return GMX_ERR_INVALID;
+  if (has_match && ctx_route_ok(cb, routes->match_route, routes->n_match_route, KM)) return GMX_ERR_INVALID;
+  // a column has one writer on the device
+  auto device_owned_mixer = [&](int c) {
+    if (c == cs->mixer_ctx_col) return true;
+    for (int i = 0; i < cs->n_mcols; ++i)
+      if (cs->mcols[i] == c) return true;
+    return false;
+  };
+  for (int c = 0; c < t.m; ++c)
+    if (routes->mixer_route[c] >= 0 && device_owned_mixer(c)) return GMX_ERR_INVALID;
+  if (has_ind && cs->ind_ctx_col >= 0 && routes->ind_route[cs->ind_ctx_col] >= 0) return GMX_ERR_INVALID;
+  if (cb->chainstep) return GMX_ERR_STATE;  // one lock-step object per bank
+  HIPCHK(hipSetDevice(g->device));
+  HIPCHK(hipStreamSynchronize(cb->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));
+  const GmxStepUpload up_before = cs->up;
+  cs->c_pos.assign(cs->S, 0);
+  {
+    const int rcp = cs_read_positions(cs, cb);
+    if (rcp) return rcp;
+  }
+  cb->moved = false;
+  const int32_t* const rt[3] = {routes->mixer_route, has_ind ? routes->ind_route : nullptr,
+                                has_match ? routes->match_route : nullptr};
+  const int nrt[3] = {t.m, K, KM};
+  for (int k = 0; k < 3; ++k) {
+    memset(&cs->c_tg[k], 0, sizeof cs->c_tg[k]);
+    if (!rt[k]) continue;
+    cs->c_tg[k].n_cols = nrt[k];
+    cs->c_tg[k].stride = 1;
+    memcpy(cs->c_tg[k].route, rt[k], 4 * (size_t)nrt[k]);
+  }
+  // don't move what nobody reads: bit_contexts, and a record array the caller owns no column of, leave the slices
+  {
+    bool own_mixer = false, own_ind = false, own_match = false;
+    for (int c = 0; c < t.m; ++c) own_mixer = own_mixer || (rt[0][c] < 0 && !device_owned_mixer(c));
+    for (int c = 0; c < K; ++c) own_ind = own_ind || (rt[1][c] < 0 && c != cs->ind_ctx_col);
+    for (int c = 0; c < KM; ++c) own_match = own_match || rt[2][c] < 0;
+    const uint32_t o_ctx = (uint32_t)((const uint8_t*)cs->ctx - cs->h_in), o_ictx = (uint32_t)((const uint8_t*)cs->ictx - cs->h_in),
+                   o_ibc = (uint32_t)((const uint8_t*)cs->ibc - cs->h_in), o_mctx = (uint32_t)((const uint8_t*)cs->mctx - cs->h_in);
+    GmxStepUpload u = cs->up;
+    u.n = 0;
+    for (int e = 0; e < cs->up.n; ++e) {
+      const uint32_t o = cs->up.off[e];
+      if (e >= cs->n_ctl && (o == o_ibc || (o == o_ctx && !own_mixer) || (o == o_ictx && !own_ind) || (o == o_mctx && !own_match)))
+        continue;
+      u.off[u.n] = o;
+      u.bps[u.n] = cs->up.bps[e];
+      u.n += 1;
+    }
+    cs->up = u;
+  }
+  cs->cb = cb;
+  cb->chainstep = cs;
+  const hipError_t e = cs_capture(cs);
+  if (e != hipSuccess) {  // the object cannot step any more: no graph of it is whole, and its steps say so
+    cs->cb = nullptr;
+    cb->chainstep = nullptr;
+    cs->up = up_before;
+    for (GmxCtxTarget& tg : cs->c_tg) memset(&tg, 0, sizeof tg);
+    cs->c_pos.clear();
+    cs->broken = true;
+    return e == hipErrorOutOfMemory ? GMX_ERR_NOMEM : hip_fail(e, "gmx_chainstep_attach_ctx: capture");
+  }
+  return GMX_OK;
+}
+extern "C" uint64_t gmx_chainstep_commit_bytes(const gmx_chainstep* cs) {
+  uint64_t n = 0;
+  if (cs)
+    for (int e = cs->n_ctl; e < cs->up.n; ++e) n += cs->up.bps[e];
+  return n;
 }
 extern "C" float* gmx_chainstep_ppm(gmx_chainstep* cs) { return (cs && cs->l) ? cs->ppm : nullptr; }
 extern "C" uint8_t* gmx_chainstep_bits(gmx_chainstep* cs) { return cs ? cs->bits : nullptr; }
@@ -648,7 +816,7 @@ static double cs_now() {
 
 extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
   if (!cs || !cs->g) return GMX_ERR_INVALID;
-  if (cs->in_flight || cs->mb_gone) return GMX_ERR_STATE;
+  if (cs->in_flight || cs->mb_gone || cs->cb_gone || cs->broken) return GMX_ERR_STATE;
   gmx_group* g = cs->g;
   const int S = cs->S;
   bool any = false, opens = false;
@@ -672,6 +840,15 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
     if (rc) return rc;
     if (hipStreamQuery(cs->mb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(cs->mb->stream));
     (void)hipGetLastError();
+  }
+  if (cs->cb) {  // whatever gmx_ctx_* calls queued on the bank's own stream between the steps
+    if (hipStreamQuery(cs->cb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(cs->cb->stream));
+    (void)hipGetLastError();
+    if (cs->cb->moved) {  // ... and where they left the streams in their bytes
+      const int rcp = cs_read_positions(cs, cs->cb);
+      if (rcp) return rcp;
+      cs->cb->moved = false;
+    }
   }
   {  // nobody else holds rows or table entries in registers, nothing of the banks' own is still in flight
     int rc = sessions_close(g, false);
@@ -725,8 +902,9 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
     if (cs->mb && (w & GMX_STEP_PREDICT)) {
       if (!cs->m_seen[s]) wd |= 8u;  // the stream's first Predict here: its context words are read wherever in a byte it is
       cs->m_seen[s] = 1;
-      cs->m_bc[s] = cs->ibc[s];
+      cs->m_bc[s] = cs->cb ? (cs->c_pos[s] == 7 ? 127u : 0u) : cs->ibc[s];  // (only "is it the byte's last bit" is read)
     }
+    if (cs->cb && (w & GMX_STEP_PREDICT)) cs->c_pos[s] = (uint8_t)((cs->c_pos[s] + 1) & 7);
     cs->what_dev[s] = wd;
   }
   cs->seq_no += 1;
@@ -747,7 +925,12 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
     mb_store_fence();
   }
   const double ta = cs_trace_on() ? cs_now() : 0.0;
+  if (cs->timed) HIPCHK(hipEventRecord(cs->t_ev[0], g->stream));
   HIPCHK(hipGraphLaunch(cs->exec[cs->steps & 1][(cs->l && opens) ? 1 : 0], g->stream));
+  if (cs->timed) {
+    HIPCHK(hipEventRecord(cs->t_ev[1], g->stream));
+    cs->timed_ok = true;
+  }
   if (cs_trace_on()) g_cs_trace.launch_s += cs_now() - ta;
   cs->in_flight = true;
   for (int s = 0; s < S; ++s) {
@@ -757,6 +940,7 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
       cs->pending[s] = 0;
     }
     if (w & GMX_STEP_PREDICT) cs->pending[s] = 1;
+    if (cs->cb && w) cs->cb->outstanding[s] = (w & GMX_STEP_PREDICT) ? 1 : 0;
     if (w) {
       g->fwd_done[s] = 0;
       if (cs->ib) cs->ib->fwd_done[s] = 0;
@@ -834,4 +1018,22 @@ extern "C" int gmx_chainstep_wait(gmx_chainstep* cs) {
 extern "C" int gmx_chainstep_step(gmx_chainstep* cs) {
   const int rc = gmx_chainstep_launch(cs);
   return rc ? rc : gmx_chainstep_wait(cs);
+}
+
+// gmx_chainstep_step with HIP events around the step's graph: what the device spent on it (0 when nothing was queued).
+extern "C" int gmx_chainstep_timed_step(gmx_chainstep* cs, float* device_ms) {
+  if (!cs || !cs->g || !device_ms) return GMX_ERR_INVALID;
+  *device_ms = 0.0f;
+  HIPCHK(hipSetDevice(cs->g->device));
+  for (hipEvent_t& ev : cs->t_ev)
+    if (!ev) HIPCHK(hipEventCreate(&ev));
+  cs->timed = true;
+  cs->timed_ok = false;
+  int rc = gmx_chainstep_launch(cs);
+  cs->timed = false;
+  if (!rc) rc = gmx_chainstep_wait(cs);
+  if (rc || !cs->timed_ok) return rc;
+  HIPCHK(hipEventSynchronize(cs->t_ev[1]));
+  HIPCHK(hipEventElapsedTime(device_ms, cs->t_ev[0], cs->t_ev[1]));
+  return GMX_OK;
 }

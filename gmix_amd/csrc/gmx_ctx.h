@@ -90,6 +90,17 @@ struct GmxCtxRunArgs {
   GmxCtxTarget tg[3];       // mixers, Indirect, Match
 };
 
+// One lock-step bit (gmx_ctx_step.h): the step's device copy of the control words and of the records.
+struct GmxCtxStepArgs {
+  uint8_t* banks;
+  const uint8_t* bits;      // [S] the bit a stream learns
+  const uint8_t* what;      // [S] GMX_STEP_*; 0: the stream sits the step out
+  uint32_t* bc;             // [S] bit_contexts of the step's records; nullable
+  int32_t n_streams;
+  int32_t pad;
+  GmxCtxTarget tg[3];       // mixers, Indirect, Match: ctx [S][n_cols] (stride, bc, bits unused)
+};
+
 // ---- checkpoint (indirect-hash.cpp:33-54): tables walked in chunks, one block per chunk
 #define GMX_CTX_CKPT_CHUNK 16384
 struct GmxCtxCkptChunk {

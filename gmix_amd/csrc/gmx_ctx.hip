@@ -11,6 +11,8 @@
 //                          along a record's columns
 //   gmx_ctx_commit_kernel  the board for the run's end (ring, recent_bits, values): a launch of its own because every
 //                          block of the expand kernel reads the board of the run's beginning
+// In the lock-step chain (gmx_chainstep_attach_ctx) a coded bit is one launch instead: gmx_ctx_step_kernel, a wave per
+// stream around gmx_ctx_step.h, which leaves the board and the tables as a run over the same bits does.
 //
 // Geometry of a run.  The board holds recent_bits as of the stream's newest Predict and new_bit, the bit coded since
 // (basic-contexts.cpp:28-34 runs at the NEXT Predict).  p = 2 recent_bits + new_bit is what record 0 sees before the
@@ -21,30 +23,9 @@
 #include <hip/hip_runtime.h>
 
 #include "gmx_ctx.h"
+#include "gmx_ctx_step.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-__device__ __forceinline__ uint32_t murmur_round(uint32_t h, uint32_t k) {
-  k *= 0xcc9e2d51u;
-  k = rotl32(k, 15);
-  k *= 0x1b873593u;
-  h ^= k;
-  h = rotl32(h, 13);
-  return h * 5u + 0xe6546b64u;
-}
-__device__ __forceinline__ uint32_t murmur_fmix(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  return h ^ (h >> 16);
-}
-// MurmurHash3_x86_32 (public domain, A. Appleby) of the 4 / 8 little-endian bytes of a key, seed 0xDEADBEEF
-__device__ __forceinline__ uint32_t murmur4(uint32_t k) { return murmur_fmix(murmur_round(0xDEADBEEFu, k) ^ 4u); }
-__device__ __forceinline__ uint32_t murmur8(uint64_t k) {
-  return murmur_fmix(murmur_round(murmur_round(0xDEADBEEFu, (uint32_t)k), (uint32_t)(k >> 32)) ^ 8u);
-}
 
 struct Geo {
   uint32_t p, nb0, fo, pos;
@@ -111,13 +92,13 @@ __global__ __launch_bounds__(64) void gmx_ctx_chain_kernel(const GmxCtxDev* __re
     cur = ((cur & hd.inner_mask) << 8) + lb;
     tab[idx] = cur;
     oc = ((oc & (uint64_t)hd.outer_mask) << 8) + lb;
-    oh = murmur8(oc);
+    oh = gmx_ctx_murmur8(oc);
     const uint32_t idx2 = oh % hd.table_size;
     if (idx2 != idx) {
       idx = idx2;
       cur = tab[idx];
     }
-    out[(size_t)f * dv->h] = murmur4(cur);
+    out[(size_t)f * dv->h] = gmx_ctx_murmur4(cur);
   }
   hs->outer_context = oc;
   hs->outer_hash = oh;
@@ -191,7 +172,7 @@ __global__ __launch_bounds__(256) void gmx_ctx_expand_kernel(const GmxCtxDev* __
         } else {
           uint64_t key = 0;
           for (int i = 0; i < vd.n_bytes; ++i) key = (key << 8) + CTX_B(c - (int)vd.bytes_to_use[i]);
-          val = murmur8(key);
+          val = gmx_ctx_murmur8(key);
         }
         break;
       case GMX_CTXK_INTERVAL:
@@ -274,6 +255,22 @@ __global__ __launch_bounds__(256) void gmx_ctx_commit_kernel(const GmxCtxDev* __
     bd->first_prediction = 0;
     bd->pos = (g.pos + g.jmax) % GMX_CTX_RING;
   }
+}
+
+// ---- one lock-step bit (gmx_ctx_step.h): a wave per stream ---------------------------------------------------------
+__global__ __launch_bounds__(64) void gmx_ctx_step_kernel(const GmxCtxDev* __restrict__ dv, GmxCtxStepArgs a) {
+  __shared__ uint32_t stage[GMX_CTX_MAX_VARS];
+  gmx_ctx_step_body(dv, a, (int)blockIdx.x, (int)threadIdx.x, stage);
+}
+
+// recent_bits, new_bit and first_prediction of every stream, gathered for one transfer (gmx_chainstep_attach_ctx)
+__global__ void gmx_ctx_heads_kernel(const GmxCtxDev* __restrict__ dv, const uint8_t* banks, int n_streams, uint32_t* out) {
+  const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (s >= n_streams) return;
+  const GmxCtxBoard* bd = (const GmxCtxBoard*)(banks + (size_t)s * dv->bank_bytes + dv->board_off);
+  out[3 * s] = bd->recent_bits;
+  out[3 * s + 1] = bd->new_bit;
+  out[3 * s + 2] = bd->first_prediction;
 }
 
 __global__ void gmx_ctx_init_kernel(const GmxCtxDev* __restrict__ dv, uint8_t* banks, int n_streams) {
@@ -361,6 +358,20 @@ extern "C" hipError_t gmx_launch_ctx_run(const GmxCtxDev* dv, int n_hash, const 
   if (e != hipSuccess) return e;
   if (marks && (e0 = hipEventRecord(marks[1], stream)) != hipSuccess) return e0;
   hipLaunchKernelGGL(gmx_ctx_commit_kernel, dim3((unsigned)a.n_streams), dim3(256), 0, stream, dv, a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t gmx_launch_ctx_step(const GmxCtxDev* dv, const GmxCtxStepArgs* args, hipStream_t stream) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gmx_ctx_step_kernel, dim3((unsigned)args->n_streams), dim3(64), 0, stream, dv, *args);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t gmx_launch_ctx_heads(const GmxCtxDev* dv, const uint8_t* banks, int n_streams, uint32_t* out,
+                                            hipStream_t stream) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gmx_ctx_heads_kernel, dim3((unsigned)((n_streams + 255) / 256)), dim3(256), 0, stream, dv, banks,
+                     n_streams, out);
   return hipGetLastError();
 }
 

@@ -38,12 +38,26 @@ struct gmx_ctx {
   uint8_t* hash_dense_d = nullptr;
   uint32_t* hash_cnt_d = nullptr;
   uint64_t* hash_off_d = nullptr;
+  // gmx_chainstep_attach_ctx: the lock-step object whose steps run this bank (the two register with each other, like a
+  // Match bank and its lock-step objects), and per stream "a Predict of a step waits for its Learn": until then the
+  // board's new_bit means nothing, and neither a run nor a reader of the board may take it for a coded bit
+  gmx_chainstep* chainstep = nullptr;
+  bool moved = false;  // a gmx_ctx_* call may have moved a stream within its byte: the object reads the boards again
+  std::vector<uint8_t> outstanding;
 };
+static void chainstep_ctx_gone(gmx_chainstep* cs);  // gmx_chainstep.inc
+static int chainstep_settle(gmx_chainstep* cs);     // ... no step of it is in flight any more
+
+// Before a gmx_ctx_* call reads or writes an attached bank: the lock-step object's steps run on the group's stream.
+static int ctx_settle(gmx_ctx* cb) { return cb->chainstep ? chainstep_settle(cb->chainstep) : GMX_OK; }
 
 extern "C" {
 hipError_t gmx_launch_ctx_run(const GmxCtxDev* dv, int n_hash, const GmxCtxRunArgs* args, hipStream_t stream,
                               hipEvent_t* marks);
 hipError_t gmx_launch_ctx_init(const GmxCtxDev* dv, uint8_t* banks, int n_streams, hipStream_t stream);
+hipError_t gmx_launch_ctx_heads(const GmxCtxDev* dv, const uint8_t* banks, int n_streams, uint32_t* out,
+                                 hipStream_t stream);
+hipError_t gmx_launch_ctx_step(const GmxCtxDev* dv, const GmxCtxStepArgs* args, hipStream_t stream);
 hipError_t gmx_launch_ctx_ckpt_count(const GmxCtxCkptArgs* a, hipStream_t stream);
 hipError_t gmx_launch_ctx_ckpt_pack(const GmxCtxCkptArgs* a, hipStream_t stream);
 hipError_t gmx_launch_ctx_ckpt_scatter(const GmxCtxCkptArgs* a, int n_hash, hipStream_t stream);
@@ -69,6 +83,8 @@ static void ctx_batch_free(gmx_ctx_batch* b) {
 extern "C" void gmx_ctx_destroy(gmx_ctx* cb) {
   if (!cb) return;
   (void)hipSetDevice(cb->device);
+  if (cb->chainstep) chainstep_ctx_gone(cb->chainstep);  // (its later steps fail; none is in flight any more)
+  cb->chainstep = nullptr;
   if (cb->stream) (void)hipStreamSynchronize(cb->stream);
   for (gmx_ctx_batch* b : cb->batches) b->cb = nullptr;  // shells, as for gmx_batch
   cb->batches.clear();
@@ -88,6 +104,12 @@ extern "C" void gmx_ctx_destroy(gmx_ctx* cb) {
 extern "C" int gmx_ctx_reset(gmx_ctx* cb) {
   if (!cb) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(cb->device));
+  {
+    int rcs = ctx_settle(cb);
+    if (rcs) return rcs;
+  }
+  std::fill(cb->outstanding.begin(), cb->outstanding.end(), 0);
+  cb->moved = true;
   HIPCHK(hipMemsetAsync(cb->banks, 0, (size_t)cb->S * cb->dev.bank_bytes, cb->stream));
   HIPCHK(gmx_launch_ctx_init(cb->dev_d, cb->banks, cb->S, cb->stream));
   HIPCHK(hipStreamSynchronize(cb->stream));
@@ -184,6 +206,7 @@ extern "C" int gmx_ctx_create(gmx_ctx** out, const gmx_ctx_desc* descs, int n_va
   }
   cb->device = device;
   cb->S = n_streams;
+  cb->outstanding.assign((size_t)n_streams, 0);
   const GmxCtxDev& d = cb->dev;
   for (int i = 0; i < d.h; ++i)
     for (uint32_t e = 0; e < d.hash[i].table_size; e += GMX_CTX_CKPT_CHUNK) {
@@ -235,6 +258,7 @@ extern "C" int gmx_ctx_sync(gmx_ctx* cb) {
 }
 extern "C" int gmx_ctx_set_cu_mask(gmx_ctx* cb, const uint32_t* mask, int n_words) {
   if (!cb || n_words < 0 || (n_words > 0 && !mask)) return GMX_ERR_INVALID;
+  if (cb->chainstep) return GMX_ERR_STATE;  // (its captured steps order themselves against the stream there is)
   HIPCHK(hipSetDevice(cb->device));
   return stream_with_cu_mask(&cb->stream, mask, n_words);
 }
@@ -440,8 +464,14 @@ extern "C" int gmx_ctx_run(gmx_ctx* cb, gmx_ctx_batch* b, uint64_t n_bits, const
   if (!cb || !b || b->cb != cb || n_bits > b->max_bits) return GMX_ERR_INVALID;
   int rc = ctx_targets_ok(cb, targets, n_bits);
   if (rc) return rc;
+  if (n_bits)
+    for (int s = 0; s < cb->S; ++s)
+      if (cb->outstanding[s]) return GMX_ERR_STATE;
   HIPCHK(hipSetDevice(cb->device));
+  rc = ctx_settle(cb);
+  if (rc) return rc;
   if (kernel_ms) *kernel_ms = 0.0f;
+  cb->moved = true;
   return ctx_launch(cb, b, n_bits, nullptr, targets, kernel_ms);
 }
 
@@ -458,12 +488,16 @@ extern "C" int gmx_ctx_run_ragged(gmx_ctx* cb, gmx_ctx_batch* b, const uint64_t*
   bool same = true;
   for (int s = 0; s < cb->S; ++s) {
     if (n_bits[s] > b->max_bits) return GMX_ERR_INVALID;
+    if (n_bits[s] && cb->outstanding[s]) return GMX_ERR_STATE;
     maxn = std::max(maxn, n_bits[s]);
     same = same && n_bits[s] == n_bits[0];
   }
   int rc = ctx_targets_ok(cb, targets, maxn);
   if (rc) return rc;
   HIPCHK(hipSetDevice(cb->device));
+  rc = ctx_settle(cb);
+  if (rc) return rc;
+  cb->moved = true;
   return ctx_launch(cb, b, maxn, same ? nullptr : n_bits, targets, nullptr);
 }
 
@@ -472,7 +506,12 @@ static uint8_t* ctx_bank(gmx_ctx* cb, int stream) { return cb->banks + (size_t)s
 
 extern "C" int gmx_ctx_blackboard_get(gmx_ctx* cb, int stream, gmx_ctx_blackboard* out) {
   if (!cb || stream < 0 || stream >= cb->S || !out) return GMX_ERR_INVALID;
+  if (cb->outstanding[stream]) return GMX_ERR_STATE;
   HIPCHK(hipSetDevice(cb->device));
+  {
+    int rcs = ctx_settle(cb);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(cb->stream));
   GmxCtxBoard bd;
   HIPCHK(hipMemcpy(&bd, ctx_bank(cb, stream) + cb->dev.board_off, sizeof bd, hipMemcpyDeviceToHost));
@@ -506,8 +545,14 @@ extern "C" int gmx_ctx_blackboard_set(gmx_ctx* cb, int stream, const gmx_ctx_bla
   memcpy(bd.ring, in->rotating_history, GMX_CTX_RING);
   memcpy(bd.values, in->values, 4 * (size_t)cb->dev.v);
   HIPCHK(hipSetDevice(cb->device));
+  {
+    int rcs = ctx_settle(cb);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(cb->stream));
   HIPCHK(hipMemcpy(ctx_bank(cb, stream) + cb->dev.board_off, &bd, sizeof bd, hipMemcpyHostToDevice));
+  cb->outstanding[stream] = 0;
+  cb->moved = true;
   return GMX_OK;
 }
 
@@ -531,6 +576,10 @@ extern "C" int gmx_ctx_export(gmx_ctx* cb, int stream, void* buf, size_t* bytes,
   const GmxCtxDev& d = cb->dev;
   const int H = d.h;
   HIPCHK(hipSetDevice(cb->device));
+  {
+    int rcs = ctx_settle(cb);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(cb->stream));
   if (H == 0) {
     if (offsets) offsets[0] = 0;
@@ -679,6 +728,10 @@ extern "C" int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t b
   if (H == 0) return GMX_OK;
   // ---- the bank
   HIPCHK(hipSetDevice(cb->device));
+  {
+    int rcs = ctx_settle(cb);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(cb->stream));
   int rc = ctx_ckpt_ready(cb);
   if (rc) return rc;
@@ -737,12 +790,20 @@ extern "C" int gmx_ctx_copy(gmx_ctx* dst, int dst_stream, gmx_ctx* src, int src_
       memcmp(dst->dev.hash, src->dev.hash, sizeof dst->dev.hash) != 0 ||
       memcmp(dst->dev.maps, src->dev.maps, sizeof dst->dev.maps) != 0)
     return GMX_ERR_INVALID;
+  if (src->outstanding[src_stream]) return GMX_ERR_STATE;
   if (dst == src && dst_stream == src_stream) return GMX_OK;
   HIPCHK(hipSetDevice(src->device));
+  {
+    int rcs = ctx_settle(src);
+    if (!rcs && dst != src) rcs = ctx_settle(dst);
+    if (rcs) return rcs;
+  }
   HIPCHK(hipStreamSynchronize(src->stream));
   if (dst != src) HIPCHK(hipStreamSynchronize(dst->stream));
   HIPCHK(hipMemcpy(ctx_bank(dst, dst_stream), ctx_bank(src, src_stream), dst->dev.bank_bytes,
                    hipMemcpyDeviceToDevice));
+  dst->outstanding[dst_stream] = 0;
+  dst->moved = true;
   return GMX_OK;
 }
 

@@ -689,7 +689,8 @@ int gmx_lstm_set_cu_mask(gmx_lstm* l, const uint32_t* mask, int n_words);
  * (recent_bits, last_byte, rotating_history, recent_bytes), for S streams on one device.  A bank is described by an
  * ordered list of V <= 64 variables; a run writes, for every bit, the values the variables have at Predict of that
  * bit -- into a debugging array of the bank's own batch and into the context columns of up to three record batches
- * of the other banks.  The adapter (dropin/) does not use these banks yet. */
+ * of the other banks.  In the lock-step chain the bank steps a bit at a time (gmx_chainstep_attach_ctx below).  The
+ * adapter (dropin/) and the per-bit sessions do not use these banks yet. */
 typedef enum gmx_ctx_kind {
   GMX_CTX_ZERO = 0,             /* always_zero */
   GMX_CTX_BIT_CONTEXT = 1,      /* bit_context = recent_bits - 1 */
@@ -811,6 +812,52 @@ int gmx_ctx_copy(gmx_ctx* dst, int dst_stream, gmx_ctx* src, int src_stream);
 /* GetMemoryUsage of the variable's object: IndirectHash 36 + 4 table_size (indirect-hash.cpp:83-89), IntervalContext
  * 256 * 4 + 8 + 4, SkipContext 4 n_bytes + 4; 0 for the fields of BasicContexts, which have no object of their own. */
 int gmx_ctx_memory_usage(gmx_ctx* cb, int var, uint64_t* bytes);
+
+/* ==== The context variables in the lock-step chain ==================================================
+ * gmx_chainstep_attach_ctx: the context variables of every stream (a gmx_ctx bank of the same stream count on the same
+ * device) step on the device as well, in one launch at the head of every step.  A route has the meaning
+ * gmx_ctx_targets gives it: one entry per column, a variable index or -1 to leave the column alone -- to the caller, or
+ * to another device-side writer (longest_match from the Match lanes, lstm_prediction_context from the LSTM lanes).
+ * (A Match model reads its context word when a byte opens and keeps it for the byte, as before: a match_route names
+ * byte-level variables, which the reference's Match contexts are.)
+ * For every stream that takes part in a step:
+ *   GMX_STEP_LEARN    the board's new_bit becomes bits[s]
+ *   GMX_STEP_PREDICT  one record of gmx_ctx_run: new_bit is folded into recent_bits; when that completes a byte, or on
+ *                     the stream's very first Predict, the ring takes the byte and every SKIP, INTERVAL and
+ *                     INDIRECT_HASH variable fires; then the routed columns of contexts[s], ind_contexts[s] and
+ *                     match_contexts[s], and bit_contexts[s] (with Indirect models or a Match bank), of this step's
+ *                     device copy are written
+ * After attach the staging arrays are ignored in the routed columns and in bit_contexts; unrouted columns keep the
+ * caller's value.  bit_contexts, and a record array in which the caller owns no column, are no longer moved by
+ * gmx_chainstep_commit or the step (gmx_chainstep_commit_bytes says what is).  Everything else about a step is
+ * unchanged.  Nothing is kept outside the bank: after a step whose streams all ended on a Learn the board and the
+ * tables are what gmx_ctx_run over the same bits leaves, and a stream may go on through either surface, from anywhere
+ * in a byte (with an LSTM streams still start at a byte boundary).  The object reads every stream's position in its
+ * byte from the board at attach and counts from there; after a gmx_ctx_run / _run_ragged, _blackboard_set, _copy or
+ * _reset on the attached bank between steps it reads the boards again before its next step.  Between a stream's Predict and its Learn the board's new_bit means
+ * nothing: gmx_ctx_run / _run_ragged with bits for that stream, gmx_ctx_blackboard_get and gmx_ctx_copy from it return
+ * GMX_ERR_STATE and touch nothing; gmx_ctx_blackboard_set and gmx_ctx_reset clear that; gmx_ctx_export / _import touch
+ * only the tables and stay allowed.
+ * All of this is checked before anything is queued or changed.  GMX_ERR_STATE: not the object's first attach, a step
+ * taken or in flight, the bank attached to another lock-step object; gmx_chainstep_attach_match after this call (a
+ * Match bank is attached first) and gmx_ctx_set_cu_mask on an attached bank return it too.  GMX_ERR_INVALID: another
+ * stream count or device; a route of the wrong length or longer than 128; an entry outside [-1, V); no mixer_route; an
+ * ind_route without Indirect models or a match_route without an attached Match bank (and the reverse); a routed mixer
+ * column that is one of the Match bank's ctx_columns or the object's mixer_ctx_col; a routed Indirect column equal to
+ * ind_ctx_col.  The two objects register with each other: after the bank is destroyed the object's steps return
+ * GMX_ERR_STATE. */
+typedef struct gmx_ctx_step_routes {
+  const int32_t* mixer_route;  int32_t n_mixer_route;   /* == M of the group; required */
+  const int32_t* ind_route;    int32_t n_ind_route;     /* == K of the Indirect bank; NULL/0 iff the object has none */
+  const int32_t* match_route;  int32_t n_match_route;   /* == K of the attached Match bank; NULL/0 iff none attached */
+} gmx_ctx_step_routes;
+int gmx_chainstep_attach_ctx(gmx_chainstep* cs, gmx_ctx* cb, const gmx_ctx_step_routes* routes);
+/* Bytes of records per stream that gmx_chainstep_commit (or the step, for a stream nobody committed) moves to the
+ * device as the object stands; 0 for NULL.  For scripts/bench_chainstep_ctx.py. */
+uint64_t gmx_chainstep_commit_bytes(const gmx_chainstep* cs);
+/* gmx_chainstep_step with HIP events recorded around the step's graph on the group's stream: *device_ms is what the
+ * device spent on the step (0 when no stream asked for anything).  For scripts/bench_chainstep_ctx.py. */
+int gmx_chainstep_timed_step(gmx_chainstep* cs, float* device_ms);
 
 #ifdef __cplusplus
 }
