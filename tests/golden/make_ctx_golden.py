@@ -1,5 +1,6 @@
 """Regenerates tests/golden/ctx_*.npz from the reference itself (build container only: it needs the reference's
-sources and g++).  ref_ctx_harness.cpp is compiled against them where they lie, into oracle/_ref/; the fixtures hold
+sources and g++).  ref_ctx_harness.cpp is compiled against them where they lie, into oracle/_ref/, by the recipe of
+oracle/ref_build/Makefile (tests/ctx_harness.py calls it and reads the harness's output); the fixtures hold
 inputs, settings, the reference's recorded results and its own coverage counters, nothing of its program text.
 
     python tests/golden/make_ctx_golden.py [--ref /path/to/reference]
@@ -7,10 +8,7 @@ inputs, settings, the reference's recorded results and its own coverage counters
 import argparse
 import ctypes as C
 import os
-import struct
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -19,13 +17,10 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ctx_common  # noqa: E402
+import ctx_harness  # noqa: E402
 from gmix_amd.ctx import desc_array  # noqa: E402
 from gmix_amd.match import match_stream  # noqa: E402
 from gmix_amd.topology import stock_context_descs  # noqa: E402
-
-TUS = ["contexts/basic-contexts.cpp", "contexts/interval-context.cpp", "contexts/skip-context.cpp",
-       "contexts/indirect-hash.cpp", "contexts/murmur-hash.cpp", "contexts/nonstationary.cpp", "contexts/run-map.cpp",
-       "memory/short-term-memory.cpp", "memory/long-term-memory.cpp", "mixer/sigmoid.cpp"]
 
 
 def popcount(i):
@@ -61,21 +56,6 @@ FIXTURES = {
 NEED = dict(same_entry=20, wraps=1)
 
 
-def build(ref):
-    out = os.path.join(ROOT, "oracle", "_ref")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, "ref_ctx_harness")
-    src = os.path.join(ref, "src")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-w", "-include", "cstring", "-I", src,
-                           os.path.join(HERE, "ref_ctx_harness.cpp")] + [os.path.join(src, t) for t in TUS] +
-                          ["-o", exe])
-    return exe
-
-
-def section_count(sec):
-    return struct.unpack_from("<I", sec, 0)[0]
-
-
 def find_boundary(descs, h, size, bits):
     """The first bit count at which hash variable h holds exactly size / 2 non-zero entries, by tests/helpers/ctx_ref.c
     -- the position is then recorded by the reference itself, and its own count is what run() asserts."""
@@ -83,12 +63,12 @@ def find_boundary(descs, h, size, bits):
     for t in range(0, len(bits), 8):
         ref.run(bits[t:t + 8], values=False)
         data, off = ref.export()
-        if section_count(data[off[h]:off[h + 1]]) == size // 2:
+        if ctx_harness.section_count(data[off[h]:off[h + 1]]) == size // 2:
             return t + 8
     raise AssertionError("no position with count == table_size / 2")
 
 
-def run(exe, name, spec):
+def run(exe, name, spec, out_dir=HERE):
     data = match_stream(spec["seed"], spec["n"])
     bits = np.unpackbits(data)
     T = len(bits)
@@ -106,49 +86,25 @@ def run(exe, name, spec):
         size = descs[hash_vars[h]].table_size
         positions.append(find_boundary(descs, h, size, bits))
         boundary = dict(position_index=len(positions) - 1, hash=h, table_size=size)
-    with tempfile.TemporaryDirectory() as td:
-        fin, fd, fout = os.path.join(td, "in.bin"), os.path.join(td, "descs.bin"), os.path.join(td, "out.bin")
-        data.tofile(fin)
-        open(fd, "wb").write(bytes(arr)[:V * C.sizeof(arr[0])])
-        subprocess.check_call([exe, fin, fd, fout] + [str(p) for p in positions], stdout=subprocess.DEVNULL)
-        raw = open(fout, "rb").read()
-    V2, T2 = struct.unpack_from("<IQ", raw, 0)
-    assert V2 == V and T2 == T
-    vals = np.frombuffer(raw, "<u4", T * V, 12).reshape(T, V)
-    off = 12 + 4 * T * V
-    (n_pos,) = struct.unpack_from("<I", raw, off)
-    off += 4
-    assert n_pos == len(positions)
-    sections, section_off, boards, dense = b"", [], [], []
-    for p in range(n_pos):
-        pos_bits, h2 = struct.unpack_from("<QI", raw, off)
-        off += 12
-        assert pos_bits == sorted(positions)[p] and h2 == H
-        row = []
-        for h in range(H):
-            (n,) = struct.unpack_from("<Q", raw, off)
-            off += 8
-            row.append(len(sections))
-            sec = raw[off:off + n]
+    rec = ctx_harness.record(data, arr, V, positions, exe)
+    assert rec["T"] == T
+    vals, same_entry, wraps, n_pos = rec["values"], rec["same_entry"], rec["wraps"], len(positions)
+    sections, section_off = b"", []
+    for row in rec["sections"]:
+        section_off.append([])
+        for sec in row:
+            section_off[-1].append(len(sections))
             sections += sec
-            off += n
-            size = descs[hash_vars[h]].table_size
-            d = not (section_count(sec) < size // 2)
-            assert n == 4 + (4 * size if d else 8 * section_count(sec)) + 12
-            dense.append(int(d))
-        row.append(len(sections))
-        section_off.append(row)
-        boards.append(np.frombuffer(raw, np.uint8, ctx_common.BOARD_BYTES, off))
-        off += ctx_common.BOARD_BYTES
-    same_entry, wraps = struct.unpack_from("<2Q", raw, off)
-    assert off + 16 == len(raw)
+        section_off[-1].append(len(sections))
+    boards = rec["boards"]
+    dense = sum(rec["dense"], [])
     # the harness records positions in ascending order
     order = np.argsort(positions, kind="stable")
     positions = [positions[i] for i in order]
     if boundary:
         boundary["position_index"] = int(np.nonzero(order == boundary["position_index"])[0][0])
         sec = sections[section_off[boundary["position_index"]][boundary["hash"]]:]
-        assert section_count(sec) == boundary["table_size"] // 2, "the reference's own count at the boundary"
+        assert ctx_harness.section_count(sec) == boundary["table_size"] // 2, "the reference's own count at the boundary"
     # byte-level variables do not move within a byte; the two per-bit kinds are their first value + bit_context
     bc = ctx_common.bit_contexts(data)
     by = vals.reshape(-1, 8, V)
@@ -164,7 +120,7 @@ def run(exe, name, spec):
     for key, least in NEED.items():
         assert meta[key] >= least, (name, key, meta[key], least)
     np.savez_compressed(
-        os.path.join(HERE, name + ".npz"), seed=spec["seed"], n_bytes=spec["n"], data=data,
+        os.path.join(out_dir, name + ".npz"), seed=spec["seed"], n_bytes=spec["n"], data=data,
         descs=np.frombuffer(bytes(arr)[:V * C.sizeof(arr[0])], np.uint8), names=np.array(names),
         byte_vals=by[:, 0, :].astype(np.uint32), positions=np.array(positions, np.uint64),
         sections=np.frombuffer(sections, np.uint8), section_off=np.array(section_off, np.uint64),
@@ -177,11 +133,12 @@ def run(exe, name, spec):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default=os.environ.get("GMX_REFERENCE", "/root/reference"))
+    ap.add_argument("--out", default=HERE, help="directory the fixtures are written to")
     a = ap.parse_args()
-    exe = build(a.ref)
+    exe = ctx_harness.build(a.ref)
     dense = {}
     for name, spec in FIXTURES.items():
-        dense[name] = run(exe, name, spec)
+        dense[name] = run(exe, name, spec, a.out)
     # The 2^8-entry tables of the stock bank need 128 non-zero entries for the dense branch: with this stream generator
     # the three of them are dense at the end of ctx_stock's 3 000 bytes and sparse at the three positions before, so
     # ctx_stock alone has both branches; ctx_tiny takes the dense branch from the start (a table of 1 entry is dense by

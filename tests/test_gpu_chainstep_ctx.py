@@ -40,16 +40,18 @@ def tiny():
 
 
 def same_entry_openings(f, bits):
-    """Per hash table: byte openings of the run at which IndirectHash's old and new index are the same entry."""
+    """Per hash table: byte openings of the run at which IndirectHash's old and new index are the same entry.  f: a
+    fixture, or a Source."""
     ref = cc.Ref(f.descs)
-    sizes = [f.descs[v].table_size for v in f.hash_vars]
-    count, prev = [0] * f.H, None
+    sizes = [d.table_size for d in f.descs if d.kind == 6]
+    H = len(sizes)
+    count, prev = [0] * H, None
     for j in range(0, len(bits), 8):
         ref.run(bits[j:j + 8], values=False)
         raw, off = ref.export()
-        idx = [int.from_bytes(raw[off[h + 1] - 4:off[h + 1]], "little") % sizes[h] for h in range(f.H)]
+        idx = [int.from_bytes(raw[off[h + 1] - 4:off[h + 1]], "little") % sizes[h] for h in range(H)]
         if prev is not None:
-            for h in range(f.H):
+            for h in range(H):
                 count[h] += idx[h] == prev[h]
         prev = idx
     return count
@@ -65,14 +67,27 @@ def columns(route, vals, pattern):
     return true, host
 
 
-def chain(oracle, S, T, offsets, with_indirect, mixer_route, t0=0, match=False, seed=90):
-    """S streams of tm's 40-input six-mixer topology, stream s coding ctx_tiny's bits from byte offsets[s], records of
-    bits [t0, t0 + T): the caller's staging arrays, the truth from ctx_ref.c (and match_ref.c), and the oracle's p /
-    outputs on the merged records."""
-    key = (S, T, tuple(offsets), with_indirect, tuple(mixer_route), t0, match, seed)
+class Source:
+    """What chain() codes: a descriptor list (its name is the cache key), the bits of its stream, and which variable is
+    bit_context."""
+
+    def __init__(self, name, descs, bits, bit_context_var):
+        self.name, self.descs, self.bits, self.bit_context_var = name, descs, bits, bit_context_var
+
+
+def tiny_source():
+    f = tiny()
+    return Source("ctx_tiny", f.descs, f.bits, f.names.index("bit_context"))
+
+
+def chain(oracle, S, T, offsets, with_indirect, mixer_route, t0=0, match=False, seed=90, src=None):
+    """S streams of tm's 40-input six-mixer topology, stream s coding the bits of src (ctx_tiny unless given) from byte
+    offsets[s], records of bits [t0, t0 + T): the caller's staging arrays, the truth from ctx_ref.c (and match_ref.c),
+    and the oracle's p / outputs on the merged records.  IND_ROUTE and MATCH_ROUTE index src's variables."""
+    f = src or tiny_source()
+    key = (S, T, tuple(offsets), with_indirect, tuple(mixer_route), t0, match, seed) + ((f.name,) if src else ())
     if key in _cache:
         return _cache[key]
-    f = tiny()
     _, z = goldenlib.load("ind_tiny_dense")
     tabs = (z["ns_next"], z["rm_next"])
     fm = mc.fixture("match_k8")
@@ -89,13 +104,13 @@ def chain(oracle, S, T, offsets, with_indirect, mixer_route, t0=0, match=False, 
         assert len(allbits) == t0 + T
         vals = ref.run(allbits)[t0:]
         bits = allbits[t0:]
-        bc = vals[:, f.names.index("bit_context")].copy()
+        bc = vals[:, f.bit_context_var].copy()
         other, act_o, pat, _ = oracle.synth(N, M, T, seed=seed + s, ctx_mode=2, zero_mod=4)
         mctx_true, mctx_host = columns(mixer_route, vals, pat)
         ipat = np.repeat(rng.integers(0, 5000, (T // 8 + 2, K)).astype(np.uint32), 8, axis=0)[:T]
         ictx_true, ictx_host = columns(IND_ROUTE, vals, ipat)
         pred, act = other.copy(), act_o.copy()
-        mctxw = vals[:, MATCH_ROUTE]
+        mctxw = vals[:, MATCH_ROUTE] if match or src is None else np.zeros((T, len(MATCH_ROUTE)), np.uint32)
         if match:
             if t0:   # (the Match models begin at t0 with the stream: their context words are the routed values)
                 raise NotImplementedError
@@ -224,6 +239,37 @@ def test_ring_wrap_general_mixers_alone(gpu, oracle):
     drive(cs, x, 0, T, pauses=pauses)
     cs.close()
     assert x["refs"][0].board().rotating_history_pos == 1049 % 1000   # (the ring of 1 000 has taken 1 049 bytes)
+    assert_ctx_state(cg, x["refs"])
+    cg.close()
+    mg.close()
+
+
+def test_64_variables_16_hash_tables_mixers_alone(gpu, oracle):
+    """Every lane of gmx_ctx_step_kernel holds a variable, sixteen of them a hash table: ctx_shapes' v64_h16 list
+    (byte_plus_recent and recent_byte at indices beyond 1, random interval maps, skips), three streams of 2 000 bits,
+    stream 1 pausing inside a byte, stream 2 joining late.  Six variables reach the mixers (a hash table, an interval,
+    a skip, byte_plus_recent at an index the reference does not have, a recent byte, bit_context); all 64 and the
+    tables are compared at the end."""
+    import ctx_shapes
+    name = ctx_shapes.LONG_RUN_CASE
+    named = ctx_shapes.descs(name)
+    kinds = [k for _, k, _ in named]
+    src = Source(name, ctx_shapes.as_descs(named), np.unpackbits(ctx_shapes.stream(name)), kinds.index("bit_context"))
+    assert (len(named), kinds.count("indirect_hash")) == (64, 16)
+    bpr = [v for v, (_, k, p) in enumerate(named) if k == "byte_plus_recent" and p["index"] > 1][0]
+    route = [kinds.index("indirect_hash"), kinds.index("interval"), kinds.index("skip"), bpr,
+             kinds.index("recent_byte"), src.bit_context_var]
+    S, T, offsets = 3, 2000, [0, 61, 500]
+    x = chain(oracle, S, T, offsets, False, route, seed=180, src=src)
+    same = np.sum([same_entry_openings(src, x["bits"][s]) for s in range(S)], axis=0)
+    sizes = [d.table_size for d in src.descs if d.kind == 6]
+    assert any(n >= 1 for n, size in zip(same, sizes) if size > 1), (same, sizes)
+    cg = gpu.CtxGroup(src.descs, S)
+    mg = gpu.MixerGroup(TOPO, S)
+    cs = gpu.ChainStep(mg)
+    cs.attach_ctx(cg, route)
+    drive(cs, x, 0, T, pauses={(2, 0): 5, (1, 3): 2, (1, 1003): 4, (0, 1992): 1})
+    cs.close()
     assert_ctx_state(cg, x["refs"])
     cg.close()
     mg.close()
