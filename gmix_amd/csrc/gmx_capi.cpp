@@ -6,6 +6,7 @@
 // GMX_ERR_NO_DEVICE -- there is no CPU fallback in the product path.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,6 +22,7 @@
 #include "../../include/gmxmix.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
+#include "gmx_mailbox.h"
 #include "gmx_ckpt.h"
 #include "gmx_ind_ckpt.h"
 #include "gmx_match.h"
@@ -1745,97 +1747,144 @@ extern "C" int gmx_debug_indirect_use_sessions(gmx_indirect* ib, int on) {
 // it stands BEFORE the Indirect models' Predict (their slots are overwritten, their indices ignored if listed).
 // The Learn calls are the usual ones (gmx_indirect_learn, gmx_bank_learn): they are only noted and travel
 // with the next forward anyway.  Same floats as the two calls.
+
+// What both entry points refuse before either bank has moved (a bad index must not leave the Indirect models
+// mid-bit), and the active-mask bits of the Indirect models' slots.
+static int chain_check_inputs(const gmx_indirect* ib, const GmxTopoDev& t, const int32_t* active_models, int n_active,
+                              uint32_t* own) {
+  if ((n_active > 0 && !active_models) || n_active > t.n) return GMX_ERR_INVALID;
+  for (int i = 0; i < n_active; ++i)
+    if (active_models[i] < 0 || active_models[i] >= t.n) return GMX_ERR_INVALID;
+  for (int i = 0; i < ib->dev.k; ++i) {
+    const int a = ib->dev.m[i].slot_a, b = ib->dev.m[i].slot_b;
+    if (a < 0 || a >= t.n || b < 0 || b >= t.n) return GMX_ERR_INVALID;
+    own[a >> 5] |= 1u << (a & 31);
+    own[b >> 5] |= 1u << (b & 31);
+  }
+  return GMX_OK;
+}
+
+// The Indirect models' predictions and active flags into the mixers' inputs at the models' slots.
+static void chain_put_indirect(const gmx_indirect* ib, const float* ipd, const uint8_t* iad, float* pred, uint32_t* mask) {
+  for (int i = 0; i < ib->dev.k; ++i) {
+    const int sl[2] = {ib->dev.m[i].slot_a, ib->dev.m[i].slot_b};
+    for (int h = 0; h < 2; ++h) {
+      pred[sl[h]] = ipd[2 * i + h];
+      if (iad[2 * i + h]) mask[sl[h] >> 5] = mask[sl[h] >> 5] | (1u << (sl[h] & 31));
+    }
+  }
+}
+
+// What gmx_chain_forward_match adds to the session route below: the attached Match bank, its contexts, and where
+// its results go.
+struct GmxChainMatch {
+  gmx_match* mb;
+  const uint32_t* ctx;
+  float* predictions;
+  uint8_t* active;
+  uint32_t* longest_match;
+};
+static const int kChainNoSlot = 1;  // no session slot for the mixers: the calls one by one instead (no status is positive)
+
+// The session route of gmx_chain_forward and, with `m`, of gmx_chain_forward_match: ONE command, ONE wait.
+static int chain_forward_sessions(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
+                                  uint32_t bit_context, const float* predictions, const int32_t* active_models,
+                                  int n_active, const uint32_t* contexts, const uint32_t* own, float* p_final,
+                                  float* out_all, float* ipd, uint8_t* iad, const GmxChainMatch* m) {
+  gmx_match* const mb = m ? m->mb : nullptr;
+  GmxIndMatchCmd mcmd;
+  if (m) {
+    // (a launch-path learn of this bank that nobody has waited for yet: the wave reads what it writes)
+    if (hipStreamQuery(mb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(mb->stream));
+    (void)hipGetLastError();
+    const int noted = mb->noted[stream];
+    mcmd = {m->ctx, kMatchStepPredict | kMatchStepTakeCtx, m->predictions, m->active, m->longest_match};
+    if (noted) mcmd.what |= kMatchStepLearn | ((uint32_t)(noted - 1) << GMX_IND_MB_MATCH_BIT_SHIFT);
+  }
+  // the mixers' command first (payload in its slot, word decided, doorbell NOT rung) ...
+  int rc = session_forward_prepare(g, stream, predictions, active_models, n_active, contexts, own);
+  if (rc) return rc == GMX_ERR_STATE ? kChainNoSlot : rc;
+  GmxSession* se = g->sessions[stream];
+  // ... then the Indirect models' forward, which rings it
+  rc = ind_session_forward(ib, stream, ind_contexts, bit_context, ipd, iad, se->word, se->slot, se->mc,
+                           m ? &mcmd : nullptr);
+  if (rc == GMX_OK) {
+    ib->fwd_done[stream] = 2;
+    if (m) {
+      mb->noted[stream] = 0;  // (it went with the command)
+      mb->fwd_done[stream] = 2;
+      mb->fwd_bc[stream] = bit_context;
+    }
+  } else {
+    // the Indirect side did not take the command (nothing of it was published): the banks' forwards as launches,
+    // their results into the payload by the host, and the mixers rung from here once its inputs are whole
+    if (rc == GMX_ERR_STATE) {
+      rc = m ? match_flush_noted(mb, stream) : GMX_OK;
+      if (m && rc == GMX_OK)
+        rc = match_forward_launch(mb, stream, m->ctx, bit_context, m->predictions, m->active, m->longest_match);
+      if (rc == GMX_OK) rc = gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ipd, iad);
+    }
+    if (rc != GMX_OK) {
+      // the prepared command still goes (it carries the learn gmx_bank_learn noted, and the mailbox
+      // protocol expects an answer to the word it was given); its forward is not one to learn from
+      mb_ring(se);
+      if (session_forward_finish(g, stream, nullptr, nullptr) == GMX_OK) se->fwd_live = false;
+      return rc;
+    }
+    GmxMbPayload* pay = &se->mc->slot[se->slot];
+    chain_put_indirect(ib, ipd, iad, pay->pred, pay->mask);
+    if (m) {
+      for (int i = 0; i < mb->dev.k; ++i) {
+        const int sl = mb->dev.m[i].slot;
+        pay->pred[sl] = m->predictions[i];
+        if (m->active[i]) pay->mask[sl >> 5] = pay->mask[sl >> 5] | (1u << (sl & 31));
+      }
+      for (int c = 0; c < ib->match_n_cols; ++c) pay->ctx[ib->match_cols[c]] = *m->longest_match;
+    }
+    mb_ring(se);
+  }
+  rc = session_forward_finish(g, stream, p_final, out_all);
+  if (rc == GMX_OK) g->fwd_done[stream] = 2;
+  return rc;
+}
+
 extern "C" int gmx_chain_forward(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
                                  uint32_t bit_context, const float* predictions, const int32_t* active_models,
                                  int n_active, const uint32_t* contexts, float* p_final, float* out_all,
                                  float* ind_predictions, uint8_t* ind_active) {
   if (!ib || !g || stream < 0 || stream >= ib->S || stream >= g->S || !ind_contexts || !predictions || !contexts)
     return GMX_ERR_INVALID;
-  if (n_active > 0 && !active_models) return GMX_ERR_INVALID;
   const GmxTopoDev& t = g->topo;
-  const int K = ib->dev.k;
-  if (n_active > t.n) return GMX_ERR_INVALID;
-  for (int i = 0; i < n_active; ++i)  // before either bank has moved: a bad index must not leave the Indirect models mid-bit
-    if (active_models[i] < 0 || active_models[i] >= t.n) return GMX_ERR_INVALID;
-  uint32_t own[GMX_MAX_INPUTS / 32] = {0};  // the active-mask bits of the Indirect models' slots
-  for (int i = 0; i < K; ++i) {
-    const int a = ib->dev.m[i].slot_a, b = ib->dev.m[i].slot_b;
-    if (a < 0 || a >= t.n || b < 0 || b >= t.n) return GMX_ERR_INVALID;
-    own[a >> 5] |= 1u << (a & 31);
-    own[b >> 5] |= 1u << (b & 31);
-  }
+  uint32_t own[GMX_MAX_INPUTS / 32] = {0};
+  if (chain_check_inputs(ib, t, active_models, n_active, own)) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(g->device));
-  float ip_[2 * GMX_IND_MAX_MODELS];  // (no allocation on a per-bit path)
-  uint8_t ia_[2 * GMX_IND_MAX_MODELS];
-  float* const ipd = ip_;
-  uint8_t* const iad = ia_;
-  const size_t n2 = (size_t)2 * K;
-  if (ib->device == g->device && ib->use_sessions && g->use_sessions && group_is_stock(g) && n_active >= 0) {
-    // the mixers' command first (payload in its slot, word decided, doorbell NOT rung) ...
-    int rc = session_forward_prepare(g, stream, predictions, active_models, n_active, contexts, own);
-    if (rc == GMX_OK) {
-      GmxSession* se = g->sessions[stream];
-      // ... then the Indirect models' forward, which rings it
-      rc = ind_session_forward(ib, stream, ind_contexts, bit_context, ipd, iad, se->word, se->slot, se->mc);
-      if (rc == GMX_OK) {
-        ib->fwd_done[stream] = 2;
-        rc = session_forward_finish(g, stream, p_final, out_all);
-        if (rc == GMX_OK) g->fwd_done[stream] = 2;
-      } else {
-        // the Indirect side did not take the command: ring the mixers ourselves once its inputs are whole
-        int rc2 = rc == GMX_ERR_STATE ? gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ipd, iad) : rc;
-        if (rc2 == GMX_OK) {
-          GmxMbPayload* pay = &se->mc->slot[se->slot];
-          for (int i = 0; i < K; ++i) {
-            const int sl[2] = {ib->dev.m[i].slot_a, ib->dev.m[i].slot_b};
-            for (int h = 0; h < 2; ++h) {
-              pay->pred[sl[h]] = ipd[2 * i + h];
-              if (iad[2 * i + h]) pay->mask[sl[h] >> 5] = pay->mask[sl[h] >> 5] | (1u << (sl[h] & 31));
-            }
-          }
-          session_ring(se);
-          rc2 = session_forward_finish(g, stream, p_final, out_all);
-          if (rc2 == GMX_OK) g->fwd_done[stream] = 2;
-        } else {
-          // the prepared command still goes (it carries the learn gmx_bank_learn noted, and the mailbox
-          // protocol expects an answer to the word it was given); its forward is not one to learn from
-          session_ring(se);
-          if (session_forward_finish(g, stream, nullptr, nullptr) == GMX_OK) se->fwd_live = false;
-        }
-        rc = rc2;
-      }
-      if (rc == GMX_OK) {
-        if (ind_predictions) memcpy(ind_predictions, ipd, n2 * 4);
-        if (ind_active) memcpy(ind_active, iad, n2);
-      }
-      return rc;
+  float ipd[2 * GMX_IND_MAX_MODELS];  // (no allocation on a per-bit path)
+  uint8_t iad[2 * GMX_IND_MAX_MODELS];
+  const size_t n2 = (size_t)2 * ib->dev.k;
+  int rc = kChainNoSlot;
+  if (ib->device == g->device && ib->use_sessions && g->use_sessions && group_is_stock(g) && n_active >= 0)
+    rc = chain_forward_sessions(ib, g, stream, ind_contexts, bit_context, predictions, active_models, n_active, contexts,
+                                own, p_final, out_all, ipd, iad, nullptr);
+  if (rc == kChainNoSlot) {
+    // the two calls, the host in between (fixed-size arrays: no allocation on a per-bit path)
+    rc = gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ipd, iad);
+    if (rc) return rc;
+    float pr[GMX_MAX_INPUTS];
+    int32_t act[GMX_MAX_INPUTS];
+    int na = 0;
+    memcpy(pr, predictions, (size_t)t.n * sizeof(float));
+    uint32_t on[GMX_MAX_INPUTS / 32] = {0};
+    if (n_active < 0) {
+      for (int idx = 0; idx < t.n; ++idx) on[idx >> 5] |= 1u << (idx & 31);
+    } else {
+      for (int i = 0; i < n_active; ++i) on[active_models[i] >> 5] |= 1u << (active_models[i] & 31);
     }
-    if (rc != GMX_ERR_STATE) return rc;  // GMX_ERR_STATE: no session slot for the mixers, the two calls instead
+    for (int w = 0; w < GMX_MAX_INPUTS / 32; ++w) on[w] &= ~own[w];
+    chain_put_indirect(ib, ipd, iad, pr, on);
+    for (int idx = 0; idx < t.n; ++idx)  // ascending, like ShortTermMemory::active_models
+      if ((on[idx >> 5] >> (idx & 31)) & 1u) act[na++] = idx;
+    rc = gmx_bank_forward(g, stream, pr, act, na, contexts, p_final, out_all);
   }
-  // the two calls, the host in between (fixed-size arrays: no allocation on a per-bit path)
-  int rc = gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ipd, iad);
-  if (rc) return rc;
-  float pr[GMX_MAX_INPUTS];
-  int32_t act[GMX_MAX_INPUTS];
-  int na = 0;
-  memcpy(pr, predictions, (size_t)t.n * sizeof(float));
-  uint32_t on[GMX_MAX_INPUTS / 32] = {0};
-  if (n_active < 0) {
-    for (int idx = 0; idx < t.n; ++idx) on[idx >> 5] |= 1u << (idx & 31);
-  } else {
-    for (int i = 0; i < n_active; ++i) on[active_models[i] >> 5] |= 1u << (active_models[i] & 31);
-  }
-  for (int w = 0; w < GMX_MAX_INPUTS / 32; ++w) on[w] &= ~own[w];
-  for (int i = 0; i < K; ++i) {
-    const int sl[2] = {ib->dev.m[i].slot_a, ib->dev.m[i].slot_b};
-    for (int h = 0; h < 2; ++h) {
-      pr[sl[h]] = ipd[2 * i + h];
-      if (iad[2 * i + h]) on[sl[h] >> 5] |= 1u << (sl[h] & 31);
-    }
-  }
-  for (int idx = 0; idx < t.n; ++idx)  // ascending, like ShortTermMemory::active_models
-    if ((on[idx >> 5] >> (idx & 31)) & 1u) act[na++] = idx;
-  rc = gmx_bank_forward(g, stream, pr, act, na, contexts, p_final, out_all);
   if (rc) return rc;
   if (ind_predictions) memcpy(ind_predictions, ipd, n2 * 4);
   if (ind_active) memcpy(ind_active, iad, n2);
@@ -1862,16 +1911,8 @@ extern "C" int gmx_chain_forward_match(gmx_indirect* ib, gmx_group* g, int strea
   const GmxTopoDev& t = g->topo;
   const int K = ib->dev.k, KM = mb->dev.k;
   // ---- everything that can be refused is refused before either bank moves
-  if (n_active > t.n) return GMX_ERR_INVALID;
-  for (int i = 0; i < n_active; ++i)
-    if (active_models[i] < 0 || active_models[i] >= t.n) return GMX_ERR_INVALID;
   uint32_t own[GMX_MAX_INPUTS / 32] = {0};  // the active-mask bits of the Indirect and the Match models' slots
-  for (int i = 0; i < K; ++i) {
-    const int a = ib->dev.m[i].slot_a, b = ib->dev.m[i].slot_b;
-    if (a < 0 || a >= t.n || b < 0 || b >= t.n) return GMX_ERR_INVALID;
-    own[a >> 5] |= 1u << (a & 31);
-    own[b >> 5] |= 1u << (b & 31);
-  }
+  if (chain_check_inputs(ib, t, active_models, n_active, own)) return GMX_ERR_INVALID;
   for (int i = 0; i < KM; ++i) {
     const int a = mb->dev.m[i].slot;
     if (a < 0 || a >= t.n) return GMX_ERR_INVALID;
@@ -1884,104 +1925,45 @@ extern "C" int gmx_chain_forward_match(gmx_indirect* ib, gmx_group* g, int strea
   float ip_[2 * GMX_IND_MAX_MODELS], mp_[GMX_MATCH_MAX_MODELS];  // (no allocation on a per-bit path)
   uint8_t ia_[2 * GMX_IND_MAX_MODELS], ma_[GMX_MATCH_MAX_MODELS];
   uint32_t lm = 0;
-  const size_t n2 = (size_t)2 * K;
-  auto results_out = [&]() {
-    if (ind_predictions) memcpy(ind_predictions, ip_, n2 * 4);
-    if (ind_active) memcpy(ind_active, ia_, n2);
-    if (match_predictions) memcpy(match_predictions, mp_, (size_t)KM * 4);
-    if (match_active) memcpy(match_active, ma_, (size_t)KM);
-    if (longest_match) *longest_match = lm;
-  };
+  int rc = kChainNoSlot;
   if (ib->device == g->device && ib->use_sessions && g->use_sessions && group_is_stock(g) && n_active >= 0 && K <= 56) {
-    const int noted = mb->noted[stream];
-    // (a launch-path learn of this bank that nobody has waited for yet: the wave reads what it writes)
-    if (hipStreamQuery(mb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(mb->stream));
-    (void)hipGetLastError();
-    int rc = session_forward_prepare(g, stream, predictions, active_models, n_active, contexts, own);
-    if (rc == GMX_OK) {
-      GmxSession* se = g->sessions[stream];
-      GmxIndMatchCmd mcmd;
-      mcmd.ctx = match_contexts;
-      mcmd.what = kMatchStepPredict | kMatchStepTakeCtx;
-      if (noted) mcmd.what |= kMatchStepLearn | ((uint32_t)(noted - 1) << GMX_IND_MB_MATCH_BIT_SHIFT);
-      mcmd.predictions = mp_;
-      mcmd.active = ma_;
-      mcmd.longest_match = &lm;
-      rc = ind_session_forward(ib, stream, ind_contexts, bit_context, ip_, ia_, se->word, se->slot, se->mc, &mcmd);
-      if (rc == GMX_OK) {
-        ib->fwd_done[stream] = 2;
-        mb->noted[stream] = 0;  // (it went with the command)
-        mb->fwd_done[stream] = 2;
-        mb->fwd_bc[stream] = bit_context;
-        rc = session_forward_finish(g, stream, p_final, out_all);
-        if (rc == GMX_OK) g->fwd_done[stream] = 2;
-      } else {
-        // the Indirect side did not take the command (nothing of it was published): both banks' forwards as launches,
-        // their results into the payload by the host, and the mixers rung from here
-        int rc2 = rc;
-        if (rc == GMX_ERR_STATE) {
-          rc2 = match_flush_noted(mb, stream);
-          if (rc2 == GMX_OK) rc2 = match_forward_launch(mb, stream, match_contexts, bit_context, mp_, ma_, &lm);
-          if (rc2 == GMX_OK) rc2 = gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ip_, ia_);
-        }
-        if (rc2 == GMX_OK) {
-          GmxMbPayload* pay = &se->mc->slot[se->slot];
-          for (int i = 0; i < K; ++i) {
-            const int sl[2] = {ib->dev.m[i].slot_a, ib->dev.m[i].slot_b};
-            for (int h = 0; h < 2; ++h) {
-              pay->pred[sl[h]] = ip_[2 * i + h];
-              if (ia_[2 * i + h]) pay->mask[sl[h] >> 5] = pay->mask[sl[h] >> 5] | (1u << (sl[h] & 31));
-            }
-          }
-          for (int i = 0; i < KM; ++i) {
-            const int sl = mb->dev.m[i].slot;
-            pay->pred[sl] = mp_[i];
-            if (ma_[i]) pay->mask[sl >> 5] = pay->mask[sl >> 5] | (1u << (sl & 31));
-          }
-          for (int c = 0; c < ib->match_n_cols; ++c) pay->ctx[ib->match_cols[c]] = lm;
-          session_ring(se);
-          rc2 = session_forward_finish(g, stream, p_final, out_all);
-          if (rc2 == GMX_OK) g->fwd_done[stream] = 2;
-        } else {
-          // the prepared command still goes (it carries the learn gmx_bank_learn noted, and the mailbox
-          // protocol expects an answer to the word it was given); its forward is not one to learn from
-          session_ring(se);
-          if (session_forward_finish(g, stream, nullptr, nullptr) == GMX_OK) se->fwd_live = false;
-        }
-        rc = rc2;
-      }
-      if (rc == GMX_OK) results_out();
-      return rc;
+    const GmxChainMatch cm = {mb, match_contexts, mp_, ma_, &lm};
+    rc = chain_forward_sessions(ib, g, stream, ind_contexts, bit_context, predictions, active_models, n_active, contexts,
+                                own, p_final, out_all, ip_, ia_, &cm);
+  }
+  if (rc == kChainNoSlot) {
+    // ---- the two calls, the host in between.  The Match forward on the launch path: the stream's wave, if one runs,
+    // keeps nothing of its Match state and steps it only when told to, so it need not stop.
+    rc = match_flush_noted(mb, stream);
+    if (rc) return rc;
+    rc = match_forward_launch(mb, stream, match_contexts, bit_context, mp_, ma_, &lm);
+    if (rc) return rc;
+    float pr[GMX_MAX_INPUTS];
+    int32_t act[GMX_MAX_INPUTS];
+    uint32_t cx[GMX_MAX_MIXERS];
+    memcpy(pr, predictions, (size_t)t.n * sizeof(float));
+    memcpy(cx, contexts, (size_t)t.m * sizeof(uint32_t));
+    for (int c = 0; c < ib->match_n_cols; ++c) cx[ib->match_cols[c]] = lm;
+    int na = n_active;
+    if (n_active >= 0) {
+      uint32_t on[GMX_MAX_INPUTS / 32] = {0};
+      for (int i = 0; i < n_active; ++i) on[active_models[i] >> 5] |= 1u << (active_models[i] & 31);
+      for (int w = 0; w < GMX_MAX_INPUTS / 32; ++w) on[w] &= ~own[w];
+      for (int i = 0; i < KM; ++i)
+        if (ma_[i]) on[mb->dev.m[i].slot >> 5] |= 1u << (mb->dev.m[i].slot & 31);
+      na = 0;
+      for (int idx = 0; idx < t.n; ++idx)  // ascending, like ShortTermMemory::active_models
+        if ((on[idx >> 5] >> (idx & 31)) & 1u) act[na++] = idx;
     }
-    if (rc != GMX_ERR_STATE) return rc;  // GMX_ERR_STATE: no session slot for the mixers, the calls one by one instead
+    for (int i = 0; i < KM; ++i) pr[mb->dev.m[i].slot] = mp_[i];
+    rc = gmx_chain_forward(ib, g, stream, ind_contexts, bit_context, pr, act, na, cx, p_final, out_all, ip_, ia_);
   }
-  // ---- the two calls, the host in between.  The Match forward on the launch path: the stream's wave, if one runs,
-  // keeps nothing of its Match state and steps it only when told to, so it need not stop.
-  int rc = match_flush_noted(mb, stream);
   if (rc) return rc;
-  rc = match_forward_launch(mb, stream, match_contexts, bit_context, mp_, ma_, &lm);
-  if (rc) return rc;
-  float pr[GMX_MAX_INPUTS];
-  int32_t act[GMX_MAX_INPUTS];
-  uint32_t cx[GMX_MAX_MIXERS];
-  memcpy(pr, predictions, (size_t)t.n * sizeof(float));
-  memcpy(cx, contexts, (size_t)t.m * sizeof(uint32_t));
-  for (int c = 0; c < ib->match_n_cols; ++c) cx[ib->match_cols[c]] = lm;
-  int na = n_active;
-  if (n_active >= 0) {
-    uint32_t on[GMX_MAX_INPUTS / 32] = {0};
-    for (int i = 0; i < n_active; ++i) on[active_models[i] >> 5] |= 1u << (active_models[i] & 31);
-    for (int w = 0; w < GMX_MAX_INPUTS / 32; ++w) on[w] &= ~own[w];
-    for (int i = 0; i < KM; ++i)
-      if (ma_[i]) on[mb->dev.m[i].slot >> 5] |= 1u << (mb->dev.m[i].slot & 31);
-    na = 0;
-    for (int idx = 0; idx < t.n; ++idx)  // ascending, like ShortTermMemory::active_models
-      if ((on[idx >> 5] >> (idx & 31)) & 1u) act[na++] = idx;
-  }
-  for (int i = 0; i < KM; ++i) pr[mb->dev.m[i].slot] = mp_[i];
-  rc = gmx_chain_forward(ib, g, stream, ind_contexts, bit_context, pr, act, na, cx, p_final, out_all, ip_, ia_);
-  if (rc) return rc;
-  results_out();
+  if (ind_predictions) memcpy(ind_predictions, ip_, (size_t)2 * K * 4);
+  if (ind_active) memcpy(ind_active, ia_, (size_t)2 * K);
+  if (match_predictions) memcpy(match_predictions, mp_, (size_t)KM * 4);
+  if (match_active) memcpy(match_active, ma_, (size_t)KM);
+  if (longest_match) *longest_match = lm;
   return GMX_OK;
 }
 

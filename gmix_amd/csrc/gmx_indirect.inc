@@ -41,6 +41,7 @@ struct gmx_indirect {
   GmxCountList counts;                          // per-stream bit counts of ragged launches
   std::vector<struct GmxIndSession*> sessions;  // per-bit sessions (gmx_indirect_session_kernel), per stream
   bool use_sessions = true;
+  bool banks_in_use_by_dead_kernel = false;  // a session wave that stopped answering may still hold them: never freed
   struct GmxIndCkptState* ckpt = nullptr;  // gmx_indirect_group_export / _import: chunk list and staging (gmx_ind_ckpt.inc), lazily
   // gmx_indirect_attach_match: the streams of this Match bank ride in lanes 56..63 of the session waves.  What a
   // wave needs of the bank is copied here at the attach (gmx_match.inc comes later in the translation unit); the two
@@ -71,18 +72,15 @@ struct GmxIndMatchCmd {
 };
 
 // ---- per-bit sessions: gmx_indirect_forward / gmx_indirect_learn without a kernel launch per call -----
-// The host side mirrors gmx_session.inc (same mailbox protocol, same bounded waits, the same count of open
-// sessions per process): the learn is only noted and travels with the next forward as one command; every
-// other entry point that touches the bank first stops the session, which writes the logit tables back.
-struct GmxIndSession {
+// The protocol and its bounded waits are gmx_mailbox.h, the blocks and the stream of a session GmxSessionHw
+// (gmx_session.inc), as for the mixers: the learn is only noted and travels with the next forward as one command;
+// every other entry point that touches the bank first stops the session, which writes the logit tables back.
+struct GmxIndSession : GmxSessionHw {
   GmxIndMbCmd* mc = nullptr;
   GmxIndMbReply* mb = nullptr;
-  bool mc_on_device = false;
-  hipStream_t stream = nullptr;
-  uint32_t seq = 0, word = 0;
   uint32_t slot = 0, live_slot = 0;  // payload slot of the newest forward published / completed
   int pending_learn = 0;       // 1 + bit: noted by gmx_indirect_learn, not yet published
-  bool launched = false, fwd_live = false, learn_inflight = false, dead = false;
+  bool fwd_live = false, learn_inflight = false;
 };
 static int ind_sessions_close(gmx_indirect* ib);
 static void ind_sessions_free(gmx_indirect* ib);
@@ -151,8 +149,10 @@ extern "C" void gmx_indirect_destroy(gmx_indirect* ib) {
   ind_ckpt_free(ib);
   for (gmx_ind_batch* b : ib->batches) b->ib = nullptr;  // shells, as for gmx_batch
   ib->batches.clear();
-  if (ib->banks) (void)hipFree(ib->banks);
-  if (ib->dev_d) (void)hipFree(ib->dev_d);
+  if (!ib->banks_in_use_by_dead_kernel) {  // (as gmx_group_destroy: leaked rather than freed under a running kernel)
+    if (ib->banks) (void)hipFree(ib->banks);
+    if (ib->dev_d) (void)hipFree(ib->dev_d);
+  }
   if (ib->ev0) (void)hipEventDestroy(ib->ev0);
   if (ib->ev1) (void)hipEventDestroy(ib->ev1);
   hipStream_t xs[] = {ib->up_stream, ib->down_stream};
@@ -533,7 +533,7 @@ extern "C" int gmx_indirect_run_ragged(gmx_indirect* ib, gmx_ind_batch* b, const
 
 // ---- per-bit sessions (see GmxIndSession above) ------------------------------------------------
 static void ind_session_note_done(GmxIndSession* se) {
-  if (se->learn_inflight && mb_load(&se->mb->done_seq) == se->word) {
+  if (se->learn_inflight && mb_load(se->done_seq) == se->word) {
     se->learn_inflight = false;
     se->fwd_live = false;
   }
@@ -541,14 +541,9 @@ static void ind_session_note_done(GmxIndSession* se) {
 
 static int ind_session_start(gmx_indirect* ib, int s) {
   GmxIndSession* se = ib->sessions[s];
-  if (se->launched) {
-    HIPCHK(hipStreamSynchronize(se->stream));
-  } else {
-    g_open_sessions.fetch_add(1);
-  }
+  int rc = session_hw_start_prologue(se);
+  if (rc) return rc;
   ind_session_note_done(se);
-  __atomic_store_n(&se->mb->state, GMX_MB_RUNNING, __ATOMIC_RELEASE);
-  se->launched = true;
   const int replay = se->fwd_live ? 1 + (int)se->live_slot : 0;
   if (ib->match) {  // the stream's Match models in lanes 56..63: the wave steps them as "stream 0" of these arguments
     GmxMatchStepArgs ma;
@@ -567,47 +562,18 @@ static int ind_session_start(gmx_indirect* ib, int s) {
   return GMX_OK;
 }
 
-static void ind_session_publish(GmxIndSession* se, uint32_t cmd) {
-  se->seq += 1;
-  se->word = (se->seq << GMX_MB_SEQ_SHIFT) | (se->slot << GMX_MB_SLOT_SHIFT) | cmd;
-  mb_store_fence();
-  __atomic_store_n(&se->mc->cmd_seq, se->word, __ATOMIC_RELEASE);
-  mb_store_fence();
+static int ind_session_dead(GmxIndSession* se) {
+  g_last_error = "per-bit Indirect session does not answer";
+  se->pending_learn = 0;
+  se->fwd_live = false;
+  return GMX_ERR_HIP;
 }
 
 // Wait until the newest command has been completed, restarting the session if it left first (bounded).
 static int ind_session_wait(gmx_indirect* ib, int s) {
   GmxIndSession* se = ib->sessions[s];
-  if (se->dead) {
-    g_last_error = "per-bit Indirect session does not answer";
-    return GMX_ERR_HIP;
-  }
-  uint64_t spins = 0;
-  timespec t_start = {0, 0};
-  while (mb_load(&se->mb->done_seq) != se->word) {
-    if ((++spins & 0xff) == 0) {
-      if (mb_load(&se->mb->state) != GMX_MB_RUNNING && mb_load(&se->mb->done_seq) != se->word) {
-        int rc = ind_session_start(ib, s);  // it left before it saw the command: the next one will
-        if (rc) return rc;
-      }
-      timespec now;
-      clock_gettime(CLOCK_MONOTONIC, &now);
-      if (spins == 0x100) t_start = now;
-      if (now.tv_sec - t_start.tv_sec > 10) {
-        g_last_error = "per-bit Indirect session does not answer";
-        ind_session_publish(se, GMX_MB_STOP);
-        se->dead = true;
-        if (se->launched) g_open_sessions.fetch_sub(1);
-        se->launched = false;
-        se->pending_learn = 0;
-        se->fwd_live = false;
-        return GMX_ERR_HIP;
-      }
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
+  int rc = mb_wait(se, kSessionTimeoutS, [&] { return ind_session_start(ib, s); });
+  if (rc) return rc == kMbDead ? ind_session_dead(se) : rc;
   ind_session_note_done(se);
   return GMX_OK;
 }
@@ -617,39 +583,17 @@ static int ind_session_wait(gmx_indirect* ib, int s) {
 static int ind_session_ensure(gmx_indirect* ib, int s, bool force) {
   if (ib->sessions.empty()) ib->sessions.assign(ib->S, nullptr);
   GmxIndSession* se = ib->sessions[s];
-  if (se && se->dead) {
-    g_last_error = "per-bit Indirect session does not answer";
-    return GMX_ERR_HIP;
-  }
-  const bool running = se && se->launched && mb_load(&se->mb->state) == GMX_MB_RUNNING;
+  if (se && se->dead) return ind_session_dead(se);
+  const bool running = se && se->launched && mb_load(se->state) == GMX_MB_RUNNING;
   if (!running && !(se && se->launched) && g_open_sessions.load() >= kMaxOpenSessions && !force) return GMX_ERR_STATE;
   if (!se) {
     se = new (std::nothrow) GmxIndSession();
     if (!se) return GMX_ERR_NOMEM;
     ib->sessions[s] = se;
-    void* p = nullptr;
-    HIPCHK(hipHostMalloc(&p, sizeof(GmxIndMbReply), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(p, 0, sizeof(GmxIndMbReply));
-    se->mb = (GmxIndMbReply*)p;
-    int large_bar = 0;
-    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, ib->device) == hipSuccess && large_bar) {
-      void* q = nullptr;
-      if (hipExtMallocWithFlags(&q, sizeof(GmxIndMbCmd), hipDeviceMallocFinegrained) == hipSuccess) {
-        if (hipMemset(q, 0, sizeof(GmxIndMbCmd)) == hipSuccess) {
-          se->mc = (GmxIndMbCmd*)q;
-          se->mc_on_device = true;
-        } else {
-          (void)hipFree(q);
-        }
-      }
-      (void)hipGetLastError();
-    }
-    if (!se->mc) {
-      HIPCHK(hipHostMalloc(&p, sizeof(GmxIndMbCmd), hipHostMallocMapped | hipHostMallocCoherent));
-      memset(p, 0, sizeof(GmxIndMbCmd));
-      se->mc = (GmxIndMbCmd*)p;
-    }
-    HIPCHK(persistent_stream_create(&se->stream));
+    int rc = session_hw_alloc(se, sizeof(GmxIndMbCmd), sizeof(GmxIndMbReply), true, ib->device);
+    se->mc = (GmxIndMbCmd*)se->cmd_seq;
+    se->mb = (GmxIndMbReply*)se->done_seq;
+    if (rc) return rc;
   }
   if (!running) {
     HIPCHK(hipStreamSynchronize(ib->stream));  // batched work on the bank is finished
@@ -667,29 +611,17 @@ static int ind_session_flush_learn(gmx_indirect* ib, int s) {
   const int bit = se->pending_learn - 1;
   se->pending_learn = 0;
   se->learn_inflight = true;
-  ind_session_publish(se, bit ? GMX_MB_LEARN1 : GMX_MB_LEARN0);
+  mb_publish(se, se->slot, bit ? GMX_MB_LEARN1 : GMX_MB_LEARN0);
   return GMX_OK;
 }
 
 static int ind_session_stop(gmx_indirect* ib, int s) {
   GmxIndSession* se = s < (int)ib->sessions.size() ? ib->sessions[s] : nullptr;
   if (!se) return GMX_OK;
-  if (se->dead) {
-    g_last_error = "per-bit Indirect session does not answer";
-    return GMX_ERR_HIP;
-  }
+  if (se->dead) return ind_session_dead(se);
   int rc = ind_session_flush_learn(ib, s);
   if (rc) return rc;
-  if (se->launched) {
-    rc = ind_session_wait(ib, s);
-    if (rc) return rc;
-    if (mb_load(&se->mb->state) == GMX_MB_RUNNING) ind_session_publish(se, GMX_MB_STOP);
-    HIPCHK(hipStreamSynchronize(se->stream));
-    __atomic_store_n(&se->mb->done_seq, se->word, __ATOMIC_RELEASE);
-    se->launched = false;
-    g_open_sessions.fetch_sub(1);
-  }
-  return GMX_OK;
+  return session_hw_stop(se, [&] { return ind_session_wait(ib, s); });
 }
 
 static void ind_sessions_drop_forward(gmx_indirect* ib, int stream) {
@@ -702,41 +634,13 @@ static void ind_sessions_drop_forward(gmx_indirect* ib, int stream) {
 }
 
 static int ind_sessions_close(gmx_indirect* ib) {
-  int first = GMX_OK;
-  for (size_t s = 0; s < ib->sessions.size(); ++s) {
-    int rc = ind_session_stop(ib, (int)s);
-    if (rc && !first) first = rc;
-  }
-  return first;
+  return sessions_stop_each(ib->sessions.size(), [&](int s) { return ind_session_stop(ib, s); });
 }
 
 static void ind_sessions_free(gmx_indirect* ib) {
   (void)ind_sessions_close(ib);
-  for (GmxIndSession* se : ib->sessions) {
-    if (!se) continue;
-    bool gone = true;
-    if (se->dead && se->stream) {  // its wave may still poll: bounded wait, and if it is still there keep its memory
-      gone = false;
-      for (int i = 0; i < 1000 && !gone; ++i) {
-        gone = hipStreamQuery(se->stream) == hipSuccess;
-        if (!gone) {
-          timespec ts = {0, 1000000};
-          nanosleep(&ts, nullptr);
-        }
-      }
-      (void)hipGetLastError();
-    } else if (se->stream) {
-      (void)hipStreamSynchronize(se->stream);
-    }
-    if (gone) {
-      if (se->stream) (void)hipStreamDestroy(se->stream);
-      if (se->mc && se->mc_on_device) (void)hipFree(se->mc);
-      if (se->mc && !se->mc_on_device) (void)hipHostFree(se->mc);
-      if (se->mb) (void)hipHostFree(se->mb);
-    }
-    delete se;
-  }
-  ib->sessions.clear();
+  // (a wave that is still there writes the bank's tables: gmx_indirect_destroy leaks them)
+  if (!sessions_release_each(ib->sessions)) ib->banks_in_use_by_dead_kernel = true;
 }
 
 // `chain`: after its Predict the wave hands the predictions to the mixers' session whose command block is
@@ -748,7 +652,7 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
   {
     // a noted learn rides along only if the wave that made its forward is still there
     GmxIndSession* se0 = s < (int)ib->sessions.size() ? ib->sessions[s] : nullptr;
-    if (se0 && se0->pending_learn && !(se0->launched && mb_load(&se0->mb->state) == GMX_MB_RUNNING)) {
+    if (se0 && se0->pending_learn && !(se0->launched && mb_load(se0->state) == GMX_MB_RUNNING)) {
       int rc = ind_session_flush_learn(ib, s);
       if (rc) return rc;
     }
@@ -783,7 +687,7 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
     cmd = se->pending_learn == 2 ? GMX_MB_LEARN1_FWD : GMX_MB_LEARN0_FWD;
     se->pending_learn = 0;
   }
-  ind_session_publish(se, cmd);
+  mb_publish(se, se->slot, cmd);
   rc = ind_session_wait(ib, s);
   if (rc) return rc;
   se->fwd_live = true;

@@ -57,23 +57,21 @@ struct gmx_lstm {
   std::vector<Range> range_read;
   std::vector<struct GmxLstmSession*> sessions;  // per-byte sessions (gmx_lstm_kernel<.., true>), per stream
   bool use_sessions = true;
+  bool banks_in_use_by_dead_kernel = false;  // a session block that stopped answering may still hold them: never freed
 };
 
 // ---- per-byte sessions: gmx_lstm_forward / gmx_lstm_perceive without a kernel launch per call -----------
-// Host side as for the Indirect models (gmx_indirect.inc; protocol, bounded waits and the process-wide count
-// of open sessions of gmx_session.inc): the Perceive is only noted and travels with the next forward as one
-// command; every other entry point that touches the bank first stops the session, which writes the model's
-// state back.  Nothing is ever replayed: Predict and Perceive are separate steps of the bank as they are of
-// the launch-per-call path, so a block that left on its idle timer in between simply comes back.
-struct GmxLstmSession {
+// The protocol and its bounded waits are gmx_mailbox.h, the blocks and the stream of a session GmxSessionHw
+// (gmx_session.inc), as for the mixers and the Indirect models: the Perceive is only noted and travels with the next
+// forward as one command; every other entry point that touches the bank first stops the session, which writes the
+// model's state back.  Nothing is ever replayed: Predict and Perceive are separate steps of the bank as they are of
+// the launch-per-call path, so a block that left on its idle timer in between simply comes back.  One payload, so
+// the slot bit of its command words is always 0.
+struct GmxLstmSession : GmxSessionHw {
   GmxLstmMbCmd* mc = nullptr;
   GmxLstmMbReply* mb = nullptr;
-  bool mc_on_device = false;
-  hipStream_t stream = nullptr;
-  uint32_t seq = 0, word = 0;
   int pending_byte = -1;       // noted by gmx_lstm_perceive, not yet published
   float pending_adam[4] = {0, 0, 0, 0};
-  bool launched = false, dead = false;
 };
 static int lstm_sessions_close(gmx_lstm* l);
 static void lstm_sessions_free(gmx_lstm* l);
@@ -158,8 +156,10 @@ extern "C" void gmx_lstm_destroy(gmx_lstm* l) {
   }
   for (gmx_lstm_batch* b : l->batches) b->l = nullptr;
   l->batches.clear();
-  if (l->banks) (void)hipFree(l->banks);
-  if (l->dev_d) (void)hipFree(l->dev_d);
+  if (!l->banks_in_use_by_dead_kernel) {  // (as gmx_group_destroy: leaked rather than freed under a running kernel)
+    if (l->banks) (void)hipFree(l->banks);
+    if (l->dev_d) (void)hipFree(l->dev_d);
+  }
   for (int k = 0; k < gmx_lstm::kAdamSlots; ++k) {
     if (l->adam_host[k]) (void)hipHostFree(l->adam_host[k]);
     if (l->adam_done[k]) (void)hipEventDestroy(l->adam_done[k]);
@@ -552,13 +552,8 @@ extern "C" int gmx_lstm_run_ragged(gmx_lstm* l, gmx_lstm_batch* b, const uint64_
 // ---- per-byte sessions (see GmxLstmSession above) -----------------------------------------------
 static int lstm_session_start(gmx_lstm* l, int s) {
   GmxLstmSession* se = l->sessions[s];
-  if (se->launched) {
-    HIPCHK(hipStreamSynchronize(se->stream));
-  } else {
-    g_open_sessions.fetch_add(1);
-  }
-  __atomic_store_n(&se->mb->state, GMX_MB_RUNNING, __ATOMIC_RELEASE);
-  se->launched = true;
+  int rc = session_hw_start_prologue(se);
+  if (rc) return rc;
   GmxLstmRunArgs a;
   memset(&a, 0, sizeof a);
   a.banks = l->banks;
@@ -572,47 +567,17 @@ static int lstm_session_start(gmx_lstm* l, int s) {
   return GMX_OK;
 }
 
-static void lstm_session_publish(GmxLstmSession* se, uint32_t cmd) {
-  se->seq += 1;
-  se->word = (se->seq << GMX_MB_SEQ_SHIFT) | cmd;
-  mb_store_fence();
-  __atomic_store_n(&se->mc->cmd_seq, se->word, __ATOMIC_RELEASE);
-  mb_store_fence();
+static int lstm_session_dead(GmxLstmSession* se) {
+  g_last_error = "per-byte LSTM session does not answer";
+  se->pending_byte = -1;
+  return GMX_ERR_HIP;
 }
 
 // Wait until the newest command has been completed, restarting the session if it left first (bounded).
 static int lstm_session_wait(gmx_lstm* l, int s) {
   GmxLstmSession* se = l->sessions[s];
-  if (se->dead) {
-    g_last_error = "per-byte LSTM session does not answer";
-    return GMX_ERR_HIP;
-  }
-  uint64_t spins = 0;
-  timespec t_start = {0, 0};
-  while (mb_load(&se->mb->done_seq) != se->word) {
-    if ((++spins & 0xff) == 0) {
-      if (mb_load(&se->mb->state) != GMX_MB_RUNNING && mb_load(&se->mb->done_seq) != se->word) {
-        int rc = lstm_session_start(l, s);  // it left before it saw the command: the next one will
-        if (rc) return rc;
-      }
-      timespec now;
-      clock_gettime(CLOCK_MONOTONIC, &now);
-      if (spins == 0x100) t_start = now;
-      if (now.tv_sec - t_start.tv_sec > 10) {
-        g_last_error = "per-byte LSTM session does not answer";
-        lstm_session_publish(se, GMX_MB_STOP);
-        se->dead = true;
-        if (se->launched) g_open_sessions.fetch_sub(1);
-        se->launched = false;
-        se->pending_byte = -1;
-        return GMX_ERR_HIP;
-      }
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  return GMX_OK;
+  int rc = mb_wait(se, kSessionTimeoutS, [&] { return lstm_session_start(l, s); });
+  return rc == kMbDead ? lstm_session_dead(se) : rc;
 }
 
 // Make sure session s exists and runs.  GMX_ERR_STATE: no session slot is free (the caller uses the
@@ -620,39 +585,17 @@ static int lstm_session_wait(gmx_lstm* l, int s) {
 static int lstm_session_ensure(gmx_lstm* l, int s, bool force) {
   if (l->sessions.empty()) l->sessions.assign(l->S, nullptr);
   GmxLstmSession* se = l->sessions[s];
-  if (se && se->dead) {
-    g_last_error = "per-byte LSTM session does not answer";
-    return GMX_ERR_HIP;
-  }
-  const bool running = se && se->launched && mb_load(&se->mb->state) == GMX_MB_RUNNING;
+  if (se && se->dead) return lstm_session_dead(se);
+  const bool running = se && se->launched && mb_load(se->state) == GMX_MB_RUNNING;
   if (!running && !(se && se->launched) && g_open_sessions.load() >= kMaxOpenSessions && !force) return GMX_ERR_STATE;
   if (!se) {
     se = new (std::nothrow) GmxLstmSession();
     if (!se) return GMX_ERR_NOMEM;
     l->sessions[s] = se;
-    void* p = nullptr;
-    HIPCHK(hipHostMalloc(&p, sizeof(GmxLstmMbReply), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(p, 0, sizeof(GmxLstmMbReply));
-    se->mb = (GmxLstmMbReply*)p;
-    int large_bar = 0;
-    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, l->device) == hipSuccess && large_bar) {
-      void* q = nullptr;
-      if (hipExtMallocWithFlags(&q, sizeof(GmxLstmMbCmd), hipDeviceMallocFinegrained) == hipSuccess) {
-        if (hipMemset(q, 0, sizeof(GmxLstmMbCmd)) == hipSuccess) {
-          se->mc = (GmxLstmMbCmd*)q;
-          se->mc_on_device = true;
-        } else {
-          (void)hipFree(q);
-        }
-      }
-      (void)hipGetLastError();
-    }
-    if (!se->mc) {
-      HIPCHK(hipHostMalloc(&p, sizeof(GmxLstmMbCmd), hipHostMallocMapped | hipHostMallocCoherent));
-      memset(p, 0, sizeof(GmxLstmMbCmd));
-      se->mc = (GmxLstmMbCmd*)p;
-    }
-    HIPCHK(persistent_stream_create(&se->stream));
+    int rc = session_hw_alloc(se, sizeof(GmxLstmMbCmd), sizeof(GmxLstmMbReply), true, l->device);
+    se->mc = (GmxLstmMbCmd*)se->cmd_seq;
+    se->mb = (GmxLstmMbReply*)se->done_seq;
+    if (rc) return rc;
   }
   if (!running) {
     HIPCHK(hipStreamSynchronize(l->stream));  // batched work on the bank is finished
@@ -676,67 +619,27 @@ static int lstm_session_flush(gmx_lstm* l, int s) {
   rc = lstm_session_wait(l, s);
   if (rc) return rc;
   lstm_session_put_perceive(se);
-  lstm_session_publish(se, GMX_MB_LEARN0);
+  mb_publish(se, 0, GMX_MB_LEARN0);
   return GMX_OK;
 }
 
 static int lstm_session_stop(gmx_lstm* l, int s) {
   GmxLstmSession* se = s < (int)l->sessions.size() ? l->sessions[s] : nullptr;
   if (!se) return GMX_OK;
-  if (se->dead) {
-    g_last_error = "per-byte LSTM session does not answer";
-    return GMX_ERR_HIP;
-  }
+  if (se->dead) return lstm_session_dead(se);
   int rc = lstm_session_flush(l, s);
   if (rc) return rc;
-  if (se->launched) {
-    rc = lstm_session_wait(l, s);
-    if (rc) return rc;
-    if (mb_load(&se->mb->state) == GMX_MB_RUNNING) lstm_session_publish(se, GMX_MB_STOP);
-    HIPCHK(hipStreamSynchronize(se->stream));
-    __atomic_store_n(&se->mb->done_seq, se->word, __ATOMIC_RELEASE);
-    se->launched = false;
-    g_open_sessions.fetch_sub(1);
-  }
-  return GMX_OK;
+  return session_hw_stop(se, [&] { return lstm_session_wait(l, s); });
 }
 
 static int lstm_sessions_close(gmx_lstm* l) {
-  int first = GMX_OK;
-  for (size_t s = 0; s < l->sessions.size(); ++s) {
-    int rc = lstm_session_stop(l, (int)s);
-    if (rc && !first) first = rc;
-  }
-  return first;
+  return sessions_stop_each(l->sessions.size(), [&](int s) { return lstm_session_stop(l, s); });
 }
 
 static void lstm_sessions_free(gmx_lstm* l) {
   (void)lstm_sessions_close(l);
-  for (GmxLstmSession* se : l->sessions) {
-    if (!se) continue;
-    bool gone = true;
-    if (se->dead && se->stream) {  // its block may still poll: bounded wait, and if it is still there keep its memory
-      gone = false;
-      for (int i = 0; i < 1000 && !gone; ++i) {
-        gone = hipStreamQuery(se->stream) == hipSuccess;
-        if (!gone) {
-          timespec ts = {0, 1000000};
-          nanosleep(&ts, nullptr);
-        }
-      }
-      (void)hipGetLastError();
-    } else if (se->stream) {
-      (void)hipStreamSynchronize(se->stream);
-    }
-    if (gone) {
-      if (se->stream) (void)hipStreamDestroy(se->stream);
-      if (se->mc && se->mc_on_device) (void)hipFree(se->mc);
-      if (se->mc && !se->mc_on_device) (void)hipHostFree(se->mc);
-      if (se->mb) (void)hipHostFree(se->mb);
-    }
-    delete se;
-  }
-  l->sessions.clear();
+  // (a block that is still there writes the model's state into the bank: gmx_lstm_destroy leaks it)
+  if (!sessions_release_each(l->sessions)) l->banks_in_use_by_dead_kernel = true;
 }
 
 // Adam's scalars of the backward pass the Perceive of the byte just predicted runs, if it runs one
@@ -774,7 +677,7 @@ static int lstm_session_forward(gmx_lstm* l, int s, int last_byte, const float* 
     lstm_session_put_perceive(se);
     cmd = GMX_MB_LEARN0_FWD;
   }
-  lstm_session_publish(se, cmd);
+  mb_publish(se, 0, cmd);
   rc = lstm_session_wait(l, s);
   if (rc) return rc;
   if (probs) memcpy(probs, (const void*)se->mb->probs, GMX_L_NO * 4);

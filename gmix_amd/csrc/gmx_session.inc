@@ -17,38 +17,29 @@
 // a few of those, so at most kMaxOpenSessions sessions are open per process: opening another
 // one in the same group stops the least recently used, and a group that cannot get one uses
 // the two-launch path for that call.
+//
+// The protocol itself (command word, wait with restart and bounded time-out, the count of open sessions) is
+// gmx_mailbox.h, which needs no HIP; the HIP half that every kind of session has (GmxSessionHw: the blocks and the
+// stream, start prologue, stop, release) comes first below and also serves gmx_indirect.inc and gmx_lstm.inc.
 
-struct GmxSession {
-  GmxMbCmd* mc = nullptr;        // commands: fine-grained device memory (host stores through the BAR) or pinned host memory
-  GmxMbReply* mb = nullptr;      // replies: host pointer == device pointer (mapped, coherent)
-  bool mc_on_device = false;
+static_assert(kMbStop == GMX_MB_STOP && kMbSlotShift == GMX_MB_SLOT_SHIFT && kMbSeqShift == GMX_MB_SEQ_SHIFT &&
+                  kMbRunning == GMX_MB_RUNNING && kMbExitIdle == GMX_MB_EXIT_IDLE,
+              "gmx_mailbox.h and the kernels speak the same protocol");
+static const long kSessionTimeoutS = 10;
+
+// ---- the HIP half of a session, the same for the mixers, the Indirect models and the LSTM -------------------
+// The protocol state (gmx_mailbox.h) with the two blocks it points into and the stream its wave lives on.  A bank's
+// own session struct derives from this and adds the typed pointers to its blocks and what it keeps per payload.
+struct GmxSessionHw : GmxMailbox {
+  bool mc_on_device = false;     // the command block is device memory (else pinned host memory)
   hipStream_t stream = nullptr;
-  uint32_t seq = 0;              // sequence number of the newest command published
-  uint32_t word = 0;             // its command word (seq << 4 | slot << 3 | cmd)
-  uint32_t slot = 0;             // payload slot of the newest forward published
-  uint32_t live_slot = 0;        // payload slot of the newest forward COMPLETED (the one a restart replays)
-  int pending_learn = 0;         // 1 + bit: gmx_bank_learn noted, not yet published
-  bool launched = false;         // an instance was started and not yet known to have left
-  bool fwd_live = false;         // a forward has completed whose learn has not (replay on restart)
-  bool learn_inflight = false;   // the newest command is that learn, on its own
-  bool dead = false;             // its wave stopped answering: every later call fails at once
-  uint64_t last_use = 0;
 };
-
-extern "C" hipError_t gmx_launch_stock_session(const GmxTopoDev* tp_dev, uint8_t* banks, int stream_idx,
-                                               GmxMbCmd* mc, GmxMbReply* mr, unsigned long long idle_ticks,
-                                               int replay_forward, int exact, unsigned lds_bytes,
-                                               hipStream_t stream);
-
-// Stores to the command block may be write-combined (BAR mapping): make them globally visible,
-// in order, before the command word follows.
-static inline void mb_store_fence() {
-#if defined(__x86_64__)
-  __builtin_ia32_sfence();
-#else
-  __atomic_thread_fence(__ATOMIC_SEQ_CST);
-#endif
-}
+#define GMX_MB_LAYOUT_CHECK(Cmd, Reply)                                                                       \
+  static_assert(offsetof(Cmd, cmd_seq) == 0 && offsetof(Reply, done_seq) == 0 && offsetof(Reply, state) == 4, \
+                #Cmd " / " #Reply ": the words GmxMailbox points at")
+GMX_MB_LAYOUT_CHECK(GmxMbCmd, GmxMbReply);
+GMX_MB_LAYOUT_CHECK(GmxIndMbCmd, GmxIndMbReply);
+GMX_MB_LAYOUT_CHECK(GmxLstmMbCmd, GmxLstmMbReply);
 
 // The stream a persistent kernel lives on.  The runtime maps streams onto a handful of hardware queues per
 // priority level (four by default), and a kernel that does not end blocks everything queued behind it on ITS
@@ -63,9 +54,130 @@ static hipError_t persistent_stream_create(hipStream_t* out) {
   return hipStreamCreateWithPriority(out, hipStreamNonBlocking, greatest);
 }
 
-static const unsigned long long kIdleTicks = 2ull * 1000 * 1000;  // 20 ms of s_memrealtime (100 MHz)
-static const int kMaxOpenSessions = 3;
-static std::atomic<int> g_open_sessions{0};
+// The reply block (mapped, coherent: host pointer == device pointer), the command block and the stream.  The command
+// block is device memory if the host can store into it and the caller allows it (measured on MI355X,
+// scripts/probe_bar_mailbox.hip: 3.0 us per round trip instead of 4.5), else pinned host memory.
+static int session_hw_alloc(GmxSessionHw* h, size_t cmd_bytes, size_t reply_bytes, bool allow_bar, int device) {
+  void* p = nullptr;
+  HIPCHK(hipHostMalloc(&p, reply_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+  memset(p, 0, reply_bytes);
+  h->done_seq = (uint32_t*)p;
+  h->state = h->done_seq + 1;
+  int large_bar = 0;
+  if (allow_bar && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) == hipSuccess && large_bar) {
+    void* q = nullptr;
+    if (hipExtMallocWithFlags(&q, cmd_bytes, hipDeviceMallocFinegrained) == hipSuccess) {
+      if (hipMemset(q, 0, cmd_bytes) == hipSuccess) {
+        h->cmd_seq = (uint32_t*)q;
+        h->mc_on_device = true;
+      } else {
+        (void)hipFree(q);
+      }
+    }
+    (void)hipGetLastError();
+  }
+  if (!h->cmd_seq) {
+    HIPCHK(hipHostMalloc(&p, cmd_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(p, 0, cmd_bytes);
+    h->cmd_seq = (uint32_t*)p;
+  }
+  HIPCHK(persistent_stream_create(&h->stream));
+  return GMX_OK;
+}
+
+// What every (re)start does before it launches the next instance; the previous one, if any, has left or is leaving.
+static int session_hw_start_prologue(GmxSessionHw* h) {
+  if (h->launched) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+  } else {
+    g_open_sessions.fetch_add(1);
+  }
+  __atomic_store_n(h->state, GMX_MB_RUNNING, __ATOMIC_RELEASE);
+  h->launched = true;
+  return GMX_OK;
+}
+
+// Stop the wave, if one was launched; `wait` is the bank's own wait for the newest command.
+template <class Wait>
+static int session_hw_stop(GmxSessionHw* h, Wait&& wait) {
+  if (!h->launched) return GMX_OK;
+  int rc = wait();
+  if (rc) return rc;
+  if (mb_load(h->state) == GMX_MB_RUNNING) mb_publish_stop(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // an instance that left on its idle timer at that very moment never saw the STOP: mark it
+  // consumed so that the next instance does not take it for a new command
+  __atomic_store_n(h->done_seq, h->word, __ATOMIC_RELEASE);
+  h->launched = false;
+  g_open_sessions.fetch_sub(1);
+  return GMX_OK;
+}
+
+// Free the stream and the blocks of a stopped session.  The wave of a dead one may still be polling: wait a bounded
+// time for it, and if it is still there leave everything allocated rather than free memory a running kernel reads
+// and writes.  False: it is still there -- and the caller must not free the banks it works on either.
+static bool session_hw_release(GmxSessionHw* h) {
+  if (h->dead && h->stream) {
+    bool gone = false;
+    for (int i = 0; i < 1000 && !gone; ++i) {
+      gone = hipStreamQuery(h->stream) == hipSuccess;
+      if (!gone) {
+        timespec ts = {0, 1000000};
+        nanosleep(&ts, nullptr);
+      }
+    }
+    (void)hipGetLastError();
+    if (!gone) return false;
+  } else if (h->stream) {
+    (void)hipStreamSynchronize(h->stream);
+  }
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (h->cmd_seq && h->mc_on_device) (void)hipFree(h->cmd_seq);
+  if (h->cmd_seq && !h->mc_on_device) (void)hipHostFree(h->cmd_seq);
+  if (h->done_seq) (void)hipHostFree(h->done_seq);
+  return true;
+}
+
+// A bank's sessions, all of them.  Stop: every session is attempted; the first failure is what the caller sees.
+template <class Stop>
+static int sessions_stop_each(size_t n, Stop&& stop) {
+  int first = GMX_OK;
+  for (size_t s = 0; s < n; ++s) {
+    int rc = stop((int)s);
+    if (rc && !first) first = rc;
+  }
+  return first;
+}
+// Release: false if the wave of a dead one is still there (the bank then leaks what that wave works on).
+template <class Se>
+static bool sessions_release_each(std::vector<Se*>& sessions) {
+  bool gone = true;
+  for (Se* se : sessions) {
+    if (!se) continue;
+    if (!session_hw_release(se)) gone = false;
+    delete se;
+  }
+  sessions.clear();
+  return gone;
+}
+
+// ---- the mixers' sessions ------------------------------------------------------------------------------------
+struct GmxSession : GmxSessionHw {
+  GmxMbCmd* mc = nullptr;        // commands: fine-grained device memory (host stores through the BAR) or pinned host memory
+  GmxMbReply* mb = nullptr;      // replies: host pointer == device pointer (mapped, coherent)
+  uint32_t slot = 0;             // payload slot of the newest forward published
+  uint32_t live_slot = 0;        // payload slot of the newest forward COMPLETED (the one a restart replays)
+  int pending_learn = 0;         // 1 + bit: gmx_bank_learn noted, not yet published
+  bool fwd_live = false;         // a forward has completed whose learn has not (replay on restart)
+  bool learn_inflight = false;   // the newest command is that learn, on its own
+  uint64_t last_use = 0;
+};
+
+extern "C" hipError_t gmx_launch_stock_session(const GmxTopoDev* tp_dev, uint8_t* banks, int stream_idx,
+                                               GmxMbCmd* mc, GmxMbReply* mr, unsigned long long idle_ticks,
+                                               int replay_forward, int exact, unsigned lds_bytes,
+                                               hipStream_t stream);
+
 static std::atomic<uint64_t> g_session_clock{0};
 
 static bool group_is_stock(const gmx_group* g) {
@@ -73,10 +185,8 @@ static bool group_is_stock(const gmx_group* g) {
   return t.n == 90 && t.l0 == 24 && t.l1 == 8 && t.n_skip == 1 && t.has_final && t.mx[23].stride == 128;
 }
 
-static uint32_t mb_load(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
-
 static void session_note_done(GmxSession* se) {
-  if (se->learn_inflight && mb_load(&se->mb->done_seq) == se->word) {
+  if (se->learn_inflight && mb_load(se->done_seq) == se->word) {
     se->learn_inflight = false;
     se->fwd_live = false;
   }
@@ -85,75 +195,29 @@ static void session_note_done(GmxSession* se) {
 // (Re)start the wave of session s; the previous instance, if any, has left or is leaving.
 static int session_start(gmx_group* g, int s) {
   GmxSession* se = g->sessions[s];
-  if (se->launched) {
-    HIPCHK(hipStreamSynchronize(se->stream));
-  } else {
-    g_open_sessions.fetch_add(1);
-  }
+  int rc = session_hw_start_prologue(se);
+  if (rc) return rc;
   session_note_done(se);
-  __atomic_store_n(&se->mb->state, GMX_MB_RUNNING, __ATOMIC_RELEASE);
-  se->launched = true;
   HIPCHK(gmx_launch_stock_session(g->topo_dev, g->banks, s, se->mc, se->mb, kIdleTicks,
                                   se->fwd_live ? 1 + (int)se->live_slot : 0, g->stock_exact ? 1 : 0,
                                   GMX_STK_LDS_BYTES(g->topo.lds_misc), se->stream));
   return GMX_OK;
 }
 
-static void session_publish(GmxSession* se, uint32_t cmd);
+static int session_dead(GmxSession* se) {
+  g_last_error = "per-bit session does not answer";
+  se->pending_learn = 0;
+  se->fwd_live = false;
+  return GMX_ERR_HIP;
+}
 
 // Wait until the newest command has been completed, restarting the session if it left first.
 static int session_wait(gmx_group* g, int s) {
   GmxSession* se = g->sessions[s];
-  if (se->dead) {
-    g_last_error = "per-bit session does not answer";
-    return GMX_ERR_HIP;
-  }
-  uint64_t spins = 0;
-  timespec t_start = {0, 0};
-  while (mb_load(&se->mb->done_seq) != se->word) {
-    if ((++spins & 0xff) == 0) {
-      if (mb_load(&se->mb->state) != GMX_MB_RUNNING && mb_load(&se->mb->done_seq) != se->word) {
-        int rc = session_start(g, s);  // it left before it saw the command: the next one will
-        if (rc) return rc;
-      }
-      timespec now;
-      clock_gettime(CLOCK_MONOTONIC, &now);
-      if (spins == 0x100) t_start = now;
-      if (now.tv_sec - t_start.tv_sec > 10) {
-        // Give up on this session for good: one stall, not one per later call.  Its wave may still
-        // be there, so the slot count is given back but the mailboxes are never freed (sessions_free).
-        g_last_error = "per-bit session does not answer";
-        session_publish(se, GMX_MB_STOP);
-        se->dead = true;
-        if (se->launched) g_open_sessions.fetch_sub(1);
-        se->launched = false;
-        se->pending_learn = 0;
-        se->fwd_live = false;
-        return GMX_ERR_HIP;
-      }
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
+  int rc = mb_wait(se, kSessionTimeoutS, [&] { return session_start(g, s); });
+  if (rc) return rc == kMbDead ? session_dead(se) : rc;
   session_note_done(se);
   return GMX_OK;
-}
-
-// The next command word; the doorbell is rung by session_ring -- or, for a chained forward, by the wave of the
-// Indirect models once it has put its predictions into the payload (gmx_chain_forward).
-static void session_next_word(GmxSession* se, uint32_t cmd) {
-  se->seq += 1;
-  se->word = (se->seq << GMX_MB_SEQ_SHIFT) | (se->slot << GMX_MB_SLOT_SHIFT) | cmd;
-}
-static void session_ring(GmxSession* se) {
-  mb_store_fence();
-  __atomic_store_n(&se->mc->cmd_seq, se->word, __ATOMIC_RELEASE);
-  mb_store_fence();
-}
-static void session_publish(GmxSession* se, uint32_t cmd) {
-  session_next_word(se, cmd);
-  session_ring(se);
 }
 
 static int session_ensure(gmx_group* g, int s, bool force);
@@ -167,7 +231,7 @@ static int session_flush_learn(gmx_group* g, int s) {
   const int bit = se->pending_learn - 1;
   se->pending_learn = 0;
   se->learn_inflight = true;
-  session_publish(se, bit ? GMX_MB_LEARN1 : GMX_MB_LEARN0);  // not waited for: the next command does that
+  mb_publish(se, se->slot, bit ? GMX_MB_LEARN1 : GMX_MB_LEARN0);  // not waited for: the next command does that
   return GMX_OK;
 }
 
@@ -176,37 +240,17 @@ static int session_flush_learn(gmx_group* g, int s) {
 static int session_stop(gmx_group* g, int s, bool keep_forward) {
   GmxSession* se = s < (int)g->sessions.size() ? g->sessions[s] : nullptr;
   if (!se) return GMX_OK;
-  if (se->dead) {
-    g_last_error = "per-bit session does not answer";
-    return GMX_ERR_HIP;
-  }
-  {
-    int rc = session_flush_learn(g, s);
-    if (rc) return rc;
-  }
-  if (se->launched) {
-    int rc = session_wait(g, s);
-    if (rc) return rc;
-    if (mb_load(&se->mb->state) == GMX_MB_RUNNING) session_publish(se, GMX_MB_STOP);
-    HIPCHK(hipStreamSynchronize(se->stream));
-    // an instance that left on its idle timer at that very moment never saw the STOP: mark it
-    // consumed so that the next instance does not take it for a new command
-    __atomic_store_n(&se->mb->done_seq, se->word, __ATOMIC_RELEASE);
-    se->launched = false;
-    g_open_sessions.fetch_sub(1);
-  }
+  if (se->dead) return session_dead(se);
+  int rc = session_flush_learn(g, s);
+  if (rc) return rc;
+  rc = session_hw_stop(se, [&] { return session_wait(g, s); });
+  if (rc) return rc;
   if (!keep_forward) se->fwd_live = false;
   return GMX_OK;
 }
 
-// Every session is attempted; the first failure is what the caller sees.
 static int sessions_close_perbit(gmx_group* g, bool keep_forward) {
-  int first = GMX_OK;
-  for (size_t s = 0; s < g->sessions.size(); ++s) {
-    int rc = session_stop(g, (int)s, keep_forward);
-    if (rc && !first) first = rc;
-  }
-  return first;
+  return sessions_stop_each(g->sessions.size(), [&](int s) { return session_stop(g, s, keep_forward); });
 }
 
 // Nothing may hold rows in registers while something else works on the banks: the per-bit sessions and the
@@ -219,35 +263,8 @@ static int sessions_close(gmx_group* g, bool keep_forward) {
 
 static void sessions_free(gmx_group* g) {
   (void)sessions_close(g, false);
-  for (GmxSession* se : g->sessions) {
-    if (!se) continue;
-    if (se->dead) {
-      // the wave may still be polling: wait a bounded time for it, and if it is still there leave the
-      // mailboxes and the stream allocated rather than free memory a running kernel reads and writes
-      bool gone = false;
-      for (int i = 0; i < 1000 && !gone; ++i) {
-        gone = !se->stream || hipStreamQuery(se->stream) == hipSuccess;
-        if (!gone) {
-          timespec ts = {0, 1000000};
-          nanosleep(&ts, nullptr);
-        }
-      }
-      (void)hipGetLastError();
-      if (!gone) {
-        g->banks_in_use_by_dead_kernel = true;  // (its rows live in the group's banks: gmx_group_destroy leaks them)
-        delete se;
-        continue;
-      }
-    } else if (se->stream) {
-      (void)hipStreamSynchronize(se->stream);
-    }
-    if (se->stream) (void)hipStreamDestroy(se->stream);
-    if (se->mc && se->mc_on_device) (void)hipFree(se->mc);
-    if (se->mc && !se->mc_on_device) (void)hipHostFree(se->mc);
-    if (se->mb) (void)hipHostFree(se->mb);
-    delete se;
-  }
-  g->sessions.clear();
+  // (a wave that is still there has its rows in the group's banks: gmx_group_destroy leaks them)
+  if (!sessions_release_each(g->sessions)) g->banks_in_use_by_dead_kernel = true;
 }
 
 // Make sure session s exists and runs.  GMX_ERR_STATE: no session slot available (the caller
@@ -256,11 +273,8 @@ static void sessions_free(gmx_group* g) {
 static int session_ensure(gmx_group* g, int s, bool force) {
   if (g->sessions.empty()) g->sessions.assign(g->S, nullptr);
   GmxSession* se = g->sessions[s];
-  if (se && se->dead) {
-    g_last_error = "per-bit session does not answer";
-    return GMX_ERR_HIP;
-  }
-  const bool running = se && se->launched && mb_load(&se->mb->state) == GMX_MB_RUNNING;
+  if (se && se->dead) return session_dead(se);
+  const bool running = se && se->launched && mb_load(se->state) == GMX_MB_RUNNING;
   if (!running && !(se && se->launched) && g_open_sessions.load() >= kMaxOpenSessions) {
     int victim = -1;
     for (int i = 0; i < g->S; ++i) {
@@ -278,32 +292,10 @@ static int session_ensure(gmx_group* g, int s, bool force) {
     se = new (std::nothrow) GmxSession();
     if (!se) return GMX_ERR_NOMEM;
     g->sessions[s] = se;
-    void* p = nullptr;
-    HIPCHK(hipHostMalloc(&p, sizeof(GmxMbReply), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(p, 0, sizeof(GmxMbReply));
-    se->mb = (GmxMbReply*)p;
-    // the command block: device memory if the host can store into it (measured on MI355X,
-    // scripts/probe_bar_mailbox.hip: 3.0 us per round trip instead of 4.5), else pinned host memory
-    int large_bar = 0;
-    if (g->mailbox_on_device &&
-        hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, g->device) == hipSuccess && large_bar) {
-      void* q = nullptr;
-      if (hipExtMallocWithFlags(&q, sizeof(GmxMbCmd), hipDeviceMallocFinegrained) == hipSuccess) {
-        if (hipMemset(q, 0, sizeof(GmxMbCmd)) == hipSuccess) {
-          se->mc = (GmxMbCmd*)q;
-          se->mc_on_device = true;
-        } else {
-          (void)hipFree(q);
-        }
-      }
-      (void)hipGetLastError();
-    }
-    if (!se->mc) {
-      HIPCHK(hipHostMalloc(&p, sizeof(GmxMbCmd), hipHostMallocMapped | hipHostMallocCoherent));
-      memset(p, 0, sizeof(GmxMbCmd));
-      se->mc = (GmxMbCmd*)p;
-    }
-    HIPCHK(persistent_stream_create(&se->stream));
+    int rc = session_hw_alloc(se, sizeof(GmxMbCmd), sizeof(GmxMbReply), g->mailbox_on_device, g->device);
+    se->mc = (GmxMbCmd*)se->cmd_seq;
+    se->mb = (GmxMbReply*)se->done_seq;
+    if (rc) return rc;
   }
   se->last_use = g_session_clock.fetch_add(1) + 1;
   if (!running) {
@@ -335,7 +327,7 @@ static int session_forward_prepare(gmx_group* g, int s, const float* predictions
     // a noted learn rides along only if the wave that made its forward is still there; after an
     // idle exit the learn goes first, on its own, through the replay path
     GmxSession* se0 = s < (int)g->sessions.size() ? g->sessions[s] : nullptr;
-    if (se0 && se0->pending_learn && !(se0->launched && mb_load(&se0->mb->state) == GMX_MB_RUNNING)) {
+    if (se0 && se0->pending_learn && !(se0->launched && mb_load(se0->state) == GMX_MB_RUNNING)) {
       int rc = session_flush_learn(g, s);
       if (rc) return rc;
     }
@@ -366,7 +358,7 @@ static int session_forward_prepare(gmx_group* g, int s, const float* predictions
     cmd = se->pending_learn == 2 ? GMX_MB_LEARN1_FWD : GMX_MB_LEARN0_FWD;
     se->pending_learn = 0;
   }
-  session_next_word(se, cmd);
+  mb_next_word(se, se->slot, cmd);
   return GMX_OK;
 }
 
@@ -386,7 +378,7 @@ static int session_forward(gmx_group* g, int s, const float* predictions, const 
                            int n_active, const uint32_t* contexts, float* p_final, float* out_all) {
   int rc = session_forward_prepare(g, s, predictions, active_models, n_active, contexts, nullptr);
   if (rc) return rc;
-  session_ring(g->sessions[s]);
+  mb_ring(g->sessions[s]);
   return session_forward_finish(g, s, p_final, out_all);
 }
 
