@@ -248,6 +248,11 @@ def lib():
     L.gmx_ctx_export.argtypes = [vp, i32, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.gmx_ctx_import.argtypes = [vp, i32, vp, C.c_size_t]
     L.gmx_ctx_copy.argtypes = [vp, i32, vp, i32]
+    L.gmx_ctx_group_export.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.gmx_ctx_group_import.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_size_t)]
+    L.gmx_ctx_group_blackboard_get.argtypes = [vp, i32, i32, C.POINTER(CtxBlackboard)]
+    L.gmx_ctx_group_blackboard_set.argtypes = [vp, i32, i32, C.POINTER(CtxBlackboard)]
+    L.gmx_debug_ctx_group_ops.argtypes = [vp]
     L.gmx_ctx_memory_usage.argtypes = [vp, i32, C.POINTER(u64)]
     L.gmx_chainstep_attach_ctx.argtypes = [vp, vp, C.POINTER(CtxStepRoutes)]
     L.gmx_chainstep_commit_bytes.argtypes = [vp]
@@ -334,4 +339,6 @@ ABI_SYMBOLS = [
     "gmx_ctx_batch_wait", "gmx_ctx_run", "gmx_ctx_run_ragged", "gmx_ctx_blackboard_get", "gmx_ctx_blackboard_set",
     "gmx_ctx_export", "gmx_ctx_import", "gmx_ctx_copy", "gmx_ctx_memory_usage", "gmx_ctx_last_kernel_ms",
     "gmx_chainstep_attach_ctx", "gmx_chainstep_commit_bytes", "gmx_chainstep_timed_step",
+    "gmx_ctx_group_export", "gmx_ctx_group_import", "gmx_ctx_group_blackboard_get", "gmx_ctx_group_blackboard_set",
+    "gmx_debug_ctx_group_ops",
 ]

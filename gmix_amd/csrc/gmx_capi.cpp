@@ -28,6 +28,7 @@
 #include "gmx_match.h"
 #include "gmx_match_ckpt.h"
 #include "gmx_ctx.h"
+#include "gmx_ctx_ckpt.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -1521,6 +1522,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 #include "gmx_match.inc"
 #include "gmx_match_ckpt.inc"
 #include "gmx_ctx.inc"
+#include "gmx_ctx_ckpt.inc"
 #include "gmx_chainstep.inc"
 
 // ---- test probes (device math against host math; not part of the product surface) --------

@@ -44,7 +44,10 @@ struct gmx_ctx {
   gmx_chainstep* chainstep = nullptr;
   bool moved = false;  // a gmx_ctx_* call may have moved a stream within its byte: the object reads the boards again
   std::vector<uint8_t> outstanding;
+  struct GmxCtxGckState* gck = nullptr;  // the group checkpoint's staging, lazily (gmx_ctx_ckpt.inc)
+  int gck_ops = 0;                       // round trips of the newest group call (gmx_debug_ctx_group_ops)
 };
+static void ctx_gck_free(gmx_ctx* cb);  // gmx_ctx_ckpt.inc
 static void chainstep_ctx_gone(gmx_chainstep* cs);  // gmx_chainstep.inc
 static int chainstep_settle(gmx_chainstep* cs);     // ... no step of it is in flight any more
 
@@ -97,6 +100,7 @@ extern "C" void gmx_ctx_destroy(gmx_ctx* cb) {
   for (hipEvent_t e : cb->ev_mark)
     if (e) (void)hipEventDestroy(e);
   count_list_free(cb->counts);
+  ctx_gck_free(cb);
   if (cb->stream) (void)hipStreamDestroy(cb->stream);
   delete cb;
 }
@@ -674,20 +678,27 @@ out:
   return ret;
 }
 
-extern "C" int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t bytes) {
-  if (!cb || stream < 0 || stream >= cb->S || (!buf && bytes)) return GMX_ERR_INVALID;
-  const GmxCtxDev& d = cb->dev;
+// gmx_ctx_import's rules over one stream's H sections -- lengths, the branch against the count, strictly ascending
+// keys below the table size, no zero value in a sparse record, the count of a dense table -- for both imports
+// (gmx_ctx_ckpt.inc).  Touches no bank.
+struct GmxCtxSection {
+  uint32_t cnt[GMX_CTX_MAX_HASH];
+  uint8_t dense[GMX_CTX_MAX_HASH];
+  uint64_t poff[GMX_CTX_MAX_HASH];       // u32 offset of a sparse table's pairs among the section's pairs
+  const uint8_t* body[GMX_CTX_MAX_HASH];  // behind the table's u32 count
+  GmxCtxHashState hs[GMX_CTX_MAX_HASH];
+  uint64_t pairs;
+};
+static int ctx_validate_section(const GmxCtxDev& d, const uint8_t* lb, size_t bytes, GmxCtxSection* sec) {
   const int H = d.h;
-  // ---- validate everything before the bank is touched
-  const uint8_t* const lb = (const uint8_t*)buf;
   const uint8_t* p = lb;
   const uint8_t* const end = lb + bytes;
-  uint32_t cnt[GMX_CTX_MAX_HASH] = {};
-  uint8_t dense[GMX_CTX_MAX_HASH] = {};
-  uint64_t poff[GMX_CTX_MAX_HASH] = {};
-  const uint8_t* body[GMX_CTX_MAX_HASH] = {};
-  GmxCtxHashState hs[GMX_CTX_MAX_HASH];
-  memset(hs, 0, sizeof hs);
+  memset(sec, 0, sizeof *sec);
+  uint32_t* const cnt = sec->cnt;
+  uint8_t* const dense = sec->dense;
+  uint64_t* const poff = sec->poff;
+  const uint8_t** const body = sec->body;
+  GmxCtxHashState* const hs = sec->hs;
   uint64_t pairs = 0;
   for (int i = 0; i < H; ++i) {
     const uint32_t size = d.hash[i].table_size;
@@ -725,6 +736,26 @@ extern "C" int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t b
     p += 12;
   }
   if (p != end) return GMX_ERR_FORMAT;
+  sec->pairs = pairs;
+  return GMX_OK;
+}
+
+extern "C" int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t bytes) {
+  if (!cb || stream < 0 || stream >= cb->S || (!buf && bytes)) return GMX_ERR_INVALID;
+  const GmxCtxDev& d = cb->dev;
+  const int H = d.h;
+  // ---- validate everything before the bank is touched
+  GmxCtxSection sec;
+  {
+    int rcv = ctx_validate_section(d, (const uint8_t*)buf, bytes, &sec);
+    if (rcv) return rcv;
+  }
+  const uint32_t* const cnt = sec.cnt;
+  const uint8_t* const dense = sec.dense;
+  const uint64_t* const poff = sec.poff;
+  const uint8_t* const* const body = sec.body;
+  const GmxCtxHashState* const hs = sec.hs;
+  const uint64_t pairs = sec.pairs;
   if (H == 0) return GMX_OK;
   // ---- the bank
   HIPCHK(hipSetDevice(cb->device));
@@ -766,12 +797,12 @@ extern "C" int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t b
       else if (cnt[i]) XCHK(hipMemcpyAsync(staged + poff[i], body[i], 8ull * cnt[i], hipMemcpyHostToDevice, cb->stream));
     }
     if (pairs) {
-      XCHK(hipMemcpyAsync(cb->hash_dense_d, dense, sizeof dense, hipMemcpyHostToDevice, cb->stream));
-      XCHK(hipMemcpyAsync(cb->hash_cnt_d, cnt, sizeof cnt, hipMemcpyHostToDevice, cb->stream));
-      XCHK(hipMemcpyAsync(cb->hash_off_d, poff, sizeof poff, hipMemcpyHostToDevice, cb->stream));
+      XCHK(hipMemcpyAsync(cb->hash_dense_d, dense, sizeof sec.dense, hipMemcpyHostToDevice, cb->stream));
+      XCHK(hipMemcpyAsync(cb->hash_cnt_d, cnt, sizeof sec.cnt, hipMemcpyHostToDevice, cb->stream));
+      XCHK(hipMemcpyAsync(cb->hash_off_d, poff, sizeof sec.poff, hipMemcpyHostToDevice, cb->stream));
       XCHK(gmx_launch_ctx_ckpt_scatter(&a, H, cb->stream));
     }
-    XCHK(hipMemcpyAsync(bank + d.hstate_off, hs, sizeof hs, hipMemcpyHostToDevice, cb->stream));
+    XCHK(hipMemcpyAsync(bank + d.hstate_off, hs, sizeof sec.hs, hipMemcpyHostToDevice, cb->stream));
     XCHK(hipStreamSynchronize(cb->stream));  // (the sources are the caller's and this frame's)
   }
 out:

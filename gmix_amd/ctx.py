@@ -1,6 +1,8 @@
 """Host-side handles of the context banks (gmx_ctx / gmx_ctx_batch of include/gmxmix.h): test and bench harness,
 like match.py for the Match models."""
+import contextlib
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -10,10 +12,28 @@ from ._lib import CtxBlackboard, CtxDesc, CtxTargets, GmxError, check
 KINDS = {"zero": 0, "bit_context": 1, "recent_byte": 2, "byte_plus_recent": 3, "interval": 4, "skip": 5,
          "indirect_hash": 6}
 BATCH_VALUES = 1  # GMX_CTX_BATCH_VALUES
+CKPT_CHUNK = 16384  # GMX_CTX_CKPT_CHUNK of csrc/gmx_ctx.h: entries a block of the checkpoint kernels walks
 
 
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+@contextlib.contextmanager
+def _stage_bytes(n):
+    """GMX_CKPT_STAGE_BYTES = n for the calls inside (the library reads it at every call); None: as it is."""
+    if n is None:
+        yield
+        return
+    old = os.environ.get("GMX_CKPT_STAGE_BYTES")
+    os.environ["GMX_CKPT_STAGE_BYTES"] = str(int(n))
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ["GMX_CKPT_STAGE_BYTES"]
+        else:
+            os.environ["GMX_CKPT_STAGE_BYTES"] = old
 
 
 def make_desc(kind, index=0, map=None, num_bits=0, bytes_to_use=(), outer_order=0, table_size=0, inner_order=0):
@@ -148,6 +168,55 @@ class CtxGroup:
     def import_(self, data, stream=0):
         buf = np.frombuffer(data or b"\0", np.uint8)
         check(self.L.gmx_ctx_import(self.h, stream, _vp(buf), len(data)), "gmx_ctx_import")
+
+    # ---- the group checkpoint (gmx_ctx_group_*, csrc/gmx_ctx_ckpt.hip)
+    def _window(self, first, count):
+        return int(first), self.S - int(first) if count is None else int(count)
+
+    def group_sizes(self, first=0, count=None):
+        """(off [count + 1], var_off [count][H + 1]) of a sizing call: nothing is packed."""
+        first, count = self._window(first, count)
+        off = (C.c_size_t * (max(count, 0) + 1))()
+        var = (C.c_size_t * (max(count, 1) * (self.H + 1)))()
+        check(self.L.gmx_ctx_group_export(self.h, first, count, None, 0, off, var), "gmx_ctx_group_export(size)")
+        return [int(o) for o in off], [[int(var[i * (self.H + 1) + j]) for j in range(self.H + 1)]
+                                       for i in range(count)]
+
+    def group_export(self, first=0, count=None, stage_bytes=None):
+        """(bytes, off [count + 1], var_off [count][H + 1]): stream first + i's sections are bytes[off[i]:off[i + 1]],
+        what export(first + i) gives.  stage_bytes: GMX_CKPT_STAGE_BYTES for the two calls."""
+        with _stage_bytes(stage_bytes):
+            off, var = self.group_sizes(first, count)
+            first, count = self._window(first, count)
+            buf = np.zeros(max(1, off[-1]), np.uint8)
+            o = (C.c_size_t * (count + 1))()
+            v = (C.c_size_t * (count * (self.H + 1)))()
+            check(self.L.gmx_ctx_group_export(self.h, first, count, _vp(buf), off[-1], o, v), "gmx_ctx_group_export")
+        assert [int(x) for x in o] == off
+        return buf[:off[-1]].tobytes(), off, var
+
+    def group_import(self, data, off, first=0, stage_bytes=None):
+        """The inverse of group_export: stream first + i takes data[off[i]:off[i + 1]].  A malformed section anywhere
+        raises GmxError(GMX_ERR_FORMAT) and leaves every bank as it was."""
+        buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
+        o = (C.c_size_t * len(off))(*[int(x) for x in off])
+        with _stage_bytes(stage_bytes):
+            check(self.L.gmx_ctx_group_import(self.h, int(first), len(off) - 1, _vp(buf), o), "gmx_ctx_group_import")
+
+    def group_blackboards(self, first=0, count=None):
+        """The blackboards of streams [first, first + count) in one gather launch and one transfer."""
+        first, count = self._window(first, count)
+        arr = (CtxBlackboard * max(count, 1))()
+        check(self.L.gmx_ctx_group_blackboard_get(self.h, first, count, arr), "gmx_ctx_group_blackboard_get")
+        return [CtxBlackboard.from_buffer_copy(arr[i]) for i in range(count)]
+
+    def set_group_blackboards(self, boards, first=0):
+        arr = (CtxBlackboard * max(len(boards), 1))(*boards)
+        check(self.L.gmx_ctx_group_blackboard_set(self.h, int(first), len(boards), arr), "gmx_ctx_group_blackboard_set")
+
+    def group_ops(self):
+        """Launches, transfers and waits of the newest group call on this bank."""
+        return self.L.gmx_debug_ctx_group_ops(self.h)
 
     def copy_from(self, src, src_stream=0, dst_stream=0):
         check(self.L.gmx_ctx_copy(self.h, dst_stream, src.h, src_stream), "gmx_ctx_copy")

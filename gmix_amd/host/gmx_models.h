@@ -15,6 +15,9 @@
 //   gmx::MatchBank     stands where LongTermMemory::history and match_memory stood (long-term-memory.h:42-53, :82) for
 //                      the Match objects of n_streams Predictors = one gmx_match.  The owner only: construction and
 //                      checkpoints; the Match objects' Predict / Learn arrive with the model adapter.
+//   gmx::CtxBank       owns the context variables of n_streams Predictors -- the context fields of BasicContexts and the
+//                      IntervalContext / SkipContext / IndirectHash objects of predictor.cpp -- as one gmx_ctx.  The
+//                      owner only: construction and checkpoints (per stream through files, a window in one call).
 //   gmx::LstmBank      stands where LongTermMemory::neuron_layer_weights / lstm_output_layer stood
 //                      (long-term-memory.h:55-76); its constructor draws the initial weights from
 //                      rand() exactly like LstmLayer's (lstm-layer.cpp:179-194), so a Predictor that
@@ -334,6 +337,158 @@ class MatchBank {
   int status_ = GMX_OK;
   std::vector<gmx_match_desc> descs_;
   std::vector<char> short_in_;
+};
+
+// ---- the context variables ---------------------------------------------------------------------
+
+// The owner of a context bank (gmx_ctx): the context fields of BasicContexts and the IntervalContext, SkipContext and
+// IndirectHash objects of n_streams Predictors.  One Add... per kind, in construction order, mirrors the reference's
+// constructor arguments; the return value is the variable's index (what a route names).  The owner only: construction
+// and checkpoints; the variables run through gmx_ctx_run or the lock step (gmx_chainstep_attach_ctx).
+class CtxBank {
+ public:
+  explicit CtxBank(int device = 0) : device_(device) {}
+  ~CtxBank() {
+    if (h_) gmx_ctx_destroy(h_);
+  }
+  CtxBank(const CtxBank&) = delete;
+  CtxBank& operator=(const CtxBank&) = delete;
+
+  int AddZero() { return Add(GMX_CTX_ZERO); }                                   // always_zero
+  int AddBitContext() { return Add(GMX_CTX_BIT_CONTEXT); }                      // bit_context
+  int AddRecentByte(int index) { return Add(GMX_CTX_RECENT_BYTE, index); }      // recent_bytes[index]; 0: last_byte
+  int AddBytePlusRecent(int index) { return Add(GMX_CTX_BYTE_PLUS_RECENT, index); }  // last_byte_plus_recent: 0
+  // IndirectHash(outer_order, table_size, inner_order) (indirect-hash.h)
+  int AddIndirectHash(int outer_order, unsigned table_size, int inner_order) {
+    gmx_ctx_desc& d = descs_[(size_t)Add(GMX_CTX_INDIRECT_HASH)];
+    d.outer_order = outer_order;
+    d.table_size = table_size;
+    d.inner_order = inner_order;
+    tables_.push_back(table_size);
+    return (int)descs_.size() - 1;
+  }
+  // IntervalContext(map, num_bits) (interval-context.h): map has 256 entries below 256
+  template <class Map>
+  int AddIntervalContext(const Map& map, int num_bits) {
+    gmx_ctx_desc& d = descs_[(size_t)Add(GMX_CTX_INTERVAL)];
+    for (int i = 0; i < 256; ++i) d.map[i] = (uint8_t)map[i];
+    d.num_bits = num_bits;
+    return (int)descs_.size() - 1;
+  }
+  // SkipContext(bytes_to_use) (skip-context.h): 1..8 entries
+  int AddSkipContext(const std::vector<int>& bytes_to_use) {
+    gmx_ctx_desc& d = descs_[(size_t)Add(GMX_CTX_SKIP)];
+    d.n_bytes = (int32_t)bytes_to_use.size();
+    for (size_t i = 0; i < bytes_to_use.size() && i < 8; ++i) d.bytes_to_use[i] = (uint8_t)bytes_to_use[i];
+    return (int)descs_.size() - 1;
+  }
+  // Once, after the last Add.
+  int Finalize(int n_streams = 1) {
+    if (h_) return GMX_OK;
+    status_ = gmx_ctx_create(&h_, descs_.data(), (int)descs_.size(), n_streams, device_);
+    return status_;
+  }
+  bool ready() const { return h_ != nullptr; }
+  int status() const { return status_; }
+  gmx_ctx* handle() { return h_; }
+  size_t size() const { return descs_.size(); }
+  size_t hashes() const { return tables_.size(); }
+  int streams() const { return h_ ? gmx_ctx_n_streams(h_) : 0; }
+
+  // One stream through the per-stream calls: IndirectHash::WriteToDisk / ReadFromDisk of the hash variables in order
+  // (indirect-hash.cpp:33-74), same bytes.  Reading takes each table's count first and the branch from table_size.
+  void WriteToDisk(std::ofstream* s, int stream = 0) {
+    if (!h_) return;
+    size_t n = 0;
+    if (Note(gmx_ctx_export(h_, stream, nullptr, &n, nullptr))) return;
+    std::vector<char> buf(n ? n : 1);
+    if (Note(gmx_ctx_export(h_, stream, buf.data(), &n, nullptr))) return;
+    s->write(buf.data(), n);
+  }
+  void ReadFromDisk(std::ifstream* s, int stream = 0) {
+    if (!h_) return;
+    std::vector<char> buf;
+    auto take = [&](size_t n) {
+      size_t at = buf.size();
+      buf.resize(at + n);
+      s->read(buf.data() + at, n);
+      return (size_t)s->gcount() == n;
+    };
+    bool whole = true;
+    for (unsigned table_size : tables_) {
+      uint32_t count = 0;
+      whole = whole && take(4);
+      memcpy(&count, buf.data() + buf.size() - 4, 4);
+      if (count > table_size) {  // (no table has that many entries: nothing says how far the section reaches)
+        Note(GMX_ERR_FORMAT);
+        return;
+      }
+      whole = whole && take(count < table_size / 2 ? (size_t)count * 8 : (size_t)table_size * 4);
+      whole = whole && take(12);
+    }
+    if (!whole) {
+      Note(GMX_ERR_FORMAT);
+      return;
+    }
+    Note(gmx_ctx_import(h_, stream, buf.data(), buf.size()));
+  }
+  // Checkpoint of streams [first, first + count) in one call (gmx_ctx_group_export / _import); count < 0: to the
+  // bank's last stream.  Stream first + i's sections -- the bytes WriteToDisk writes for it -- are
+  // buf[off[i] .. off[i + 1]).  After Finalize.
+  int ExportGroup(std::vector<char>* buf, std::vector<size_t>* off, int first = 0, int count = -1) {
+    if (!h_) return GMX_ERR_STATE;
+    if (count < 0) count = streams() - first;
+    if (count < 1) return GMX_ERR_INVALID;
+    off->assign((size_t)count + 1, 0);
+    int rc = gmx_ctx_group_export(h_, first, count, nullptr, 0, off->data(), nullptr);
+    if (rc) return rc;
+    buf->resize(off->back() ? off->back() : 1);
+    rc = gmx_ctx_group_export(h_, first, count, buf->data(), buf->size(), off->data(), nullptr);
+    if (rc == GMX_OK) buf->resize(off->back());
+    return rc;
+  }
+  // GMX_ERR_FORMAT, and no bank touched, when any section is malformed.  The blackboards stay (SetBoards).
+  int ImportGroup(const std::vector<char>& buf, const std::vector<size_t>& off, int first = 0) {
+    if (!h_) return GMX_ERR_STATE;
+    if (off.size() < 2 || off.back() > buf.size()) return GMX_ERR_INVALID;
+    return gmx_ctx_group_import(h_, first, (int)off.size() - 1, buf.data(), off.data());
+  }
+  // The blackboards of a window (gmx_ctx_group_blackboard_get / _set): ShortTermMemory's share of the checkpoint.
+  int Boards(std::vector<gmx_ctx_blackboard>* out, int first = 0, int count = -1) {
+    if (!h_) return GMX_ERR_STATE;
+    if (count < 0) count = streams() - first;
+    if (count < 1) return GMX_ERR_INVALID;
+    out->resize((size_t)count);
+    return gmx_ctx_group_blackboard_get(h_, first, count, out->data());
+  }
+  int SetBoards(const std::vector<gmx_ctx_blackboard>& in, int first = 0) {
+    if (!h_) return GMX_ERR_STATE;
+    if (in.empty()) return GMX_ERR_INVALID;
+    return gmx_ctx_group_blackboard_set(h_, first, (int)in.size(), in.data());
+  }
+
+ private:
+  int Add(int kind, int index = 0) {
+    gmx_ctx_desc d;
+    memset(&d, 0, sizeof d);
+    d.kind = kind;
+    d.index = index;
+    descs_.push_back(d);
+    return (int)descs_.size() - 1;
+  }
+  bool Note(int rc) {
+    if (rc != GMX_OK && status_ == GMX_OK) {
+      status_ = rc;
+      fprintf(stderr, "gmx::CtxBank: %s %s\n", gmx_strerror(rc), gmx_last_error());
+    }
+    return rc != GMX_OK;
+  }
+
+  int device_;
+  gmx_ctx* h_ = nullptr;
+  int status_ = GMX_OK;
+  std::vector<gmx_ctx_desc> descs_;
+  std::vector<unsigned> tables_;
 };
 
 // ---- LSTM ------------------------------------------------------------------------------------

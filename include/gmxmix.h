@@ -806,6 +806,31 @@ int gmx_ctx_blackboard_set(gmx_ctx* cb, int stream, const gmx_ctx_blackboard* in
  * dense one -- returns GMX_ERR_FORMAT otherwise, and leaves the blackboard alone. */
 int gmx_ctx_export(gmx_ctx* cb, int stream, void* buf, size_t* bytes, size_t* offsets /* [H + 1] */);
 int gmx_ctx_import(gmx_ctx* cb, int stream, const void* buf, size_t bytes);
+
+/* Checkpoint streams [first, first + count) of a context bank in one call; non-zero entries are counted and packed on
+ * the device and every stream's sections are assembled there.  Stream first + i's section -- byte for byte what
+ * gmx_ctx_export gives for it -- lies at buf + off[i], off[i + 1] - off[i] bytes; off has count + 1 entries and is
+ * always filled.  var_off (nullable, [count][H + 1]) receives where each variable's section begins inside its stream's
+ * section (gmx_ctx_export's offsets).  buf == NULL: off and var_off only.  GMX_ERR_INVALID if cap < off[count]; nothing
+ * is written to buf then.  count >= 1 and the window inside the bank, else GMX_ERR_INVALID.  A bank without hash
+ * variables has empty sections: off all zero, nothing launched.  The sections pass through one device buffer and two
+ * pinned host buffers in slices of consecutive streams that fit 64 MiB together (GMX_CKPT_STAGE_BYTES in the
+ * environment, read at every call, replaces the cap; a slice is never less than one stream): the launches, transfers
+ * and waits of a call depend on the number of slices, not on count. */
+int gmx_ctx_group_export(gmx_ctx* cb, int first, int count, void* buf, size_t cap, size_t* off /* [count + 1] */,
+                         size_t* var_off /* nullable [count][H + 1] */);
+/* The inverse (off[0] need not be 0; the sections are contiguous).  Every section is validated as gmx_ctx_import
+ * validates it BEFORE any bank is touched: a bad section anywhere (GMX_ERR_FORMAT) leaves all banks as they were.
+ * Like gmx_ctx_import it leaves the blackboards alone. */
+int gmx_ctx_group_import(gmx_ctx* cb, int first, int count, const void* buf, const size_t* off /* [count + 1] */);
+/* count blackboards in one gather or scatter launch and one transfer, with the meaning of gmx_ctx_blackboard_get /
+ * _set.  set validates all count boards before any is written: one bad board (GMX_ERR_INVALID) changes nothing.  On an
+ * attached bank (gmx_chainstep_attach_ctx) get returns GMX_ERR_STATE and touches nothing if any stream of the window
+ * stands between a Predict and its Learn; set clears that and makes the lock-step object read the boards again. */
+int gmx_ctx_group_blackboard_get(gmx_ctx* cb, int first, int count, gmx_ctx_blackboard* out /* [count] */);
+int gmx_ctx_group_blackboard_set(gmx_ctx* cb, int first, int count, const gmx_ctx_blackboard* in /* [count] */);
+/* Debugging: launches, transfers and waits of the newest of the four calls above on this bank. */
+int gmx_debug_ctx_group_ops(const gmx_ctx* cb);
 /* Tables, hash states and blackboard of one stream into another, between banks of the same variables on the same
  * device.  (No entry point of this library locks: as everywhere, a handle is used by one thread at a time.) */
 int gmx_ctx_copy(gmx_ctx* dst, int dst_stream, gmx_ctx* src, int src_stream);
