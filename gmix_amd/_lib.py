@@ -258,6 +258,10 @@ def lib():
     L.gmx_chainstep_commit_bytes.argtypes = [vp]
     L.gmx_chainstep_commit_bytes.restype = u64
     L.gmx_chainstep_timed_step.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gmx_ctx_learn.argtypes = [vp, i32, i32]
+    L.gmx_ctx_forward.argtypes = [vp, i32, vp, C.POINTER(u32)]
+    L.gmx_indirect_attach_ctx.argtypes = [vp, vp, C.POINTER(CtxStepRoutes)]
+    L.gmx_chain_forward_ctx.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gmx_lockstep_create.argtypes = [C.POINTER(vp), vp, C.c_uint]
     L.gmx_lockstep_destroy.argtypes = [vp]
     L.gmx_lockstep_destroy.restype = None
@@ -341,4 +345,5 @@ ABI_SYMBOLS = [
     "gmx_chainstep_attach_ctx", "gmx_chainstep_commit_bytes", "gmx_chainstep_timed_step",
     "gmx_ctx_group_export", "gmx_ctx_group_import", "gmx_ctx_group_blackboard_get", "gmx_ctx_group_blackboard_set",
     "gmx_debug_ctx_group_ops",
+    "gmx_ctx_learn", "gmx_ctx_forward", "gmx_indirect_attach_ctx", "gmx_chain_forward_ctx",
 ]

@@ -1788,12 +1788,42 @@ struct GmxChainMatch {
 };
 static const int kChainNoSlot = 1;  // no session slot for the mixers: the calls one by one instead (no status is positive)
 
-// The session route of gmx_chain_forward and, with `m`, of gmx_chain_forward_match: ONE command, ONE wait.
+// What gmx_chain_forward_ctx adds: the attached context bank, and where its results go.  With it the routed columns
+// of ind_contexts, of the Match contexts and of the mixers' contexts, and bit_context, are the bank's.
+struct GmxChainCtx {
+  gmx_ctx* cb;
+  uint32_t* values;       // [V], not null (the launch route merges from it)
+  bool want_values;       // the caller asked for them: the wave returns them too
+  uint32_t* bit_context;  // not null
+};
+// The records of a bit with the routed columns taken from the bank's values (the launch routes).
+static void chain_ctx_merge(const gmx_ctx* cb, int base, int n, const uint32_t* vals, const uint32_t* own, uint32_t* out) {
+  for (int c = 0; c < n; ++c) {
+    const int32_t rt = cb->routes[base + c];
+    out[c] = rt >= 0 ? vals[rt] : (own ? own[c] : 0u);
+  }
+}
+
+// The session route of gmx_chain_forward, with `m` of gmx_chain_forward_match and with `cx` of gmx_chain_forward_ctx:
+// ONE command, ONE wait.
 static int chain_forward_sessions(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
                                   uint32_t bit_context, const float* predictions, const int32_t* active_models,
                                   int n_active, const uint32_t* contexts, const uint32_t* own, float* p_final,
-                                  float* out_all, float* ipd, uint8_t* iad, const GmxChainMatch* m) {
+                                  float* out_all, float* ipd, uint8_t* iad, const GmxChainMatch* m,
+                                  const GmxChainCtx* cx = nullptr) {
   gmx_match* const mb = m ? m->mb : nullptr;
+  gmx_ctx* const cb = cx ? cx->cb : nullptr;
+  GmxIndCtxCmd ccmd = {0, nullptr, nullptr};
+  if (cx) {
+    // (a launch-path step of this bank that nobody has waited for yet: the wave reads what it writes)
+    if (hipStreamQuery(cb->stream) != hipSuccess) HIPCHK(hipStreamSynchronize(cb->stream));
+    (void)hipGetLastError();
+    ccmd.what = GMX_STEP_PREDICT | (cx->want_values ? GMX_CTX_WAVE_VALUES : 0u) |
+                (cb->wave_fresh[stream] ? 0u : GMX_CTX_WAVE_RELOAD);
+    if (cb->noted[stream]) ccmd.what |= GMX_STEP_LEARN | ((uint32_t)(cb->noted[stream] - 1) << GMX_CTX_WAVE_BIT_SHIFT);
+    ccmd.values = cx->values;
+    ccmd.bit_context = cx->bit_context;
+  }
   GmxIndMatchCmd mcmd;
   if (m) {
     // (a launch-path learn of this bank that nobody has waited for yet: the wave reads what it writes)
@@ -1809,9 +1839,19 @@ static int chain_forward_sessions(gmx_indirect* ib, gmx_group* g, int stream, co
   GmxSession* se = g->sessions[stream];
   // ... then the Indirect models' forward, which rings it
   rc = ind_session_forward(ib, stream, ind_contexts, bit_context, ipd, iad, se->word, se->slot, se->mc,
-                           m ? &mcmd : nullptr);
+                           m ? &mcmd : nullptr, cx ? &ccmd : nullptr);
+  bool ctx_by_launch = false;
   if (rc == GMX_OK) {
     ib->fwd_done[stream] = 2;
+    if (cx) {
+      if (cb->noted[stream]) {  // (it went with the command)
+        cb->noted[stream] = 0;
+        cb->n_noted -= 1;
+      }
+      cb->outstanding[stream] = 1;
+      cb->wave_fresh[stream] = 1;
+      bit_context = *cx->bit_context;
+    }
     if (m) {
       mb->noted[stream] = 0;  // (it went with the command)
       mb->fwd_done[stream] = 2;
@@ -1821,10 +1861,27 @@ static int chain_forward_sessions(gmx_indirect* ib, gmx_group* g, int stream, co
     // the Indirect side did not take the command (nothing of it was published): the banks' forwards as launches,
     // their results into the payload by the host, and the mixers rung from here once its inputs are whole
     if (rc == GMX_ERR_STATE) {
-      rc = m ? match_flush_noted(mb, stream) : GMX_OK;
+      uint32_t icm[GMX_IND_MAX_MODELS], mcm[GMX_MATCH_MAX_MODELS];
+      const uint32_t* ic = ind_contexts;
+      const uint32_t* mc = m ? m->ctx : nullptr;
+      rc = GMX_OK;
+      if (cx) {
+        rc = ctx_forward_launch(cb, stream, cx->values, cx->bit_context);
+        if (rc == GMX_OK) {
+          ctx_by_launch = true;
+          bit_context = *cx->bit_context;
+          chain_ctx_merge(cb, GMX_CTX_WAVE_ROUTE_IND, ib->dev.k, cx->values, ind_contexts, icm);
+          ic = icm;
+          if (m) {
+            chain_ctx_merge(cb, GMX_CTX_WAVE_ROUTE_MATCH, mb->dev.k, cx->values, m->ctx, mcm);
+            mc = mcm;
+          }
+        }
+      }
+      if (rc == GMX_OK && m) rc = match_flush_noted(mb, stream);
       if (m && rc == GMX_OK)
-        rc = match_forward_launch(mb, stream, m->ctx, bit_context, m->predictions, m->active, m->longest_match);
-      if (rc == GMX_OK) rc = gmx_indirect_forward(ib, stream, ind_contexts, bit_context, ipd, iad);
+        rc = match_forward_launch(mb, stream, mc, bit_context, m->predictions, m->active, m->longest_match);
+      if (rc == GMX_OK) rc = gmx_indirect_forward(ib, stream, ic, bit_context, ipd, iad);
     }
     if (rc != GMX_OK) {
       // the prepared command still goes (it carries the learn gmx_bank_learn noted, and the mailbox
@@ -1843,6 +1900,11 @@ static int chain_forward_sessions(gmx_indirect* ib, gmx_group* g, int stream, co
       }
       for (int c = 0; c < ib->match_n_cols; ++c) pay->ctx[ib->match_cols[c]] = *m->longest_match;
     }
+    if (ctx_by_launch)
+      for (int c = 0; c < g->topo.m; ++c) {
+        const int32_t rt = cb->routes[GMX_CTX_WAVE_ROUTE_MIXER + c];
+        if (rt >= 0) pay->ctx[c] = cx->values[rt];
+      }
     mb_ring(se);
   }
   rc = session_forward_finish(g, stream, p_final, out_all);
@@ -1966,6 +2028,83 @@ extern "C" int gmx_chain_forward_match(gmx_indirect* ib, gmx_group* g, int strea
   if (match_predictions) memcpy(match_predictions, mp_, (size_t)KM * 4);
   if (match_active) memcpy(match_active, ma_, (size_t)KM);
   if (longest_match) *longest_match = lm;
+  return GMX_OK;
+}
+
+// ---- context variables + Match models + Indirect models -> mixers: the host sends one bit ------------------------
+// gmx_ctx_forward on the bank attached to `ib` (gmx_indirect_attach_ctx), then gmx_chain_forward_match -- or
+// gmx_chain_forward when no Match bank is attached -- with the routed columns of the three record sets and
+// bit_context taken from the bank.  Under gmx_chain_forward's own conditions for its one-round-trip path the context
+// variables step at the head of the chained forward in the Indirect models' session wave
+// (gmx_indirect_session_kernel<.., true>): ONE command, ONE wait, and no context word crosses the link.  A learn
+// gmx_ctx_learn noted rides in the same command (GmxIndMbCmd::ctx_what).
+extern "C" int gmx_chain_forward_ctx(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
+                                     const uint32_t* match_contexts, const float* predictions,
+                                     const int32_t* active_models, int n_active, const uint32_t* contexts,
+                                     float* p_final, float* out_all, float* ind_predictions, uint8_t* ind_active,
+                                     float* match_predictions, uint8_t* match_active, uint32_t* longest_match,
+                                     uint32_t* ctx_values, uint32_t* bit_context) {
+  if (!ib || !g || stream < 0 || stream >= ib->S || stream >= g->S || !predictions || !contexts) return GMX_ERR_INVALID;
+  if (n_active > 0 && !active_models) return GMX_ERR_INVALID;
+  gmx_ctx* const cb = ib->ctx;
+  if (!cb) return GMX_ERR_STATE;  // nothing attached
+  gmx_match* const mb = ib->match;
+  const GmxTopoDev& t = g->topo;
+  const int K = ib->dev.k, KM = mb ? mb->dev.k : 0;
+  // ---- everything that can be refused is refused before any bank moves
+  if (t.m != ib->ctx_n_mixer_cols) return GMX_ERR_INVALID;  // the mixer route was made for another M
+  if ((cb->own_ind && !ind_contexts) || (mb && cb->own_match && !match_contexts)) return GMX_ERR_INVALID;
+  uint32_t own[GMX_MAX_INPUTS / 32] = {0};  // the active-mask bits of the Indirect and the Match models' slots
+  if (chain_check_inputs(ib, t, active_models, n_active, own)) return GMX_ERR_INVALID;
+  for (int i = 0; i < KM; ++i) {
+    const int a = mb->dev.m[i].slot;
+    if (a < 0 || a >= t.n) return GMX_ERR_INVALID;
+    own[a >> 5] |= 1u << (a & 31);
+  }
+  for (int c = 0; c < ib->match_n_cols; ++c)
+    if (ib->match_cols[c] >= t.m || cb->routes[GMX_CTX_WAVE_ROUTE_MIXER + ib->match_cols[c]] >= 0) return GMX_ERR_INVALID;
+  if (cb->outstanding[stream]) return GMX_ERR_STATE;  // a Predict moves state: one per bit
+  if (mb && mb->fwd_done[stream]) return GMX_ERR_STATE;
+  HIPCHK(hipSetDevice(g->device));
+  float ip_[2 * GMX_IND_MAX_MODELS], mp_[GMX_MATCH_MAX_MODELS];  // (no allocation on a per-bit path)
+  uint8_t ia_[2 * GMX_IND_MAX_MODELS], ma_[GMX_MATCH_MAX_MODELS];
+  uint32_t vals[GMX_CTX_MAX_VARS];
+  uint32_t lm = 0, bc = 0;
+  int rc = kChainNoSlot;
+  if (ib->device == g->device && ib->use_sessions && g->use_sessions && group_is_stock(g) && n_active >= 0 &&
+      (!mb || K <= 56)) {
+    const GmxChainMatch cm = {mb, match_contexts, mp_, ma_, &lm};
+    const GmxChainCtx cc = {cb, vals, ctx_values != nullptr, &bc};
+    rc = chain_forward_sessions(ib, g, stream, ind_contexts, 0u, predictions, active_models, n_active, contexts, own,
+                                p_final, out_all, ip_, ia_, mb ? &cm : nullptr, &cc);
+    if (rc == GMX_OK && ctx_values && cb->outstanding[stream]) memcpy(ctx_values, vals, 4 * (size_t)cb->dev.v);
+  }
+  if (rc == kChainNoSlot) {
+    // ---- the launches one after the other, the host in between: the stream's wave, if one runs, does not touch the
+    // context bank then
+    rc = ctx_forward_launch(cb, stream, vals, &bc);
+    if (rc) return rc;
+    uint32_t icm[GMX_IND_MAX_MODELS], mcm[GMX_MATCH_MAX_MODELS], xcm[GMX_MAX_MIXERS];
+    chain_ctx_merge(cb, GMX_CTX_WAVE_ROUTE_IND, K, vals, ind_contexts, icm);
+    chain_ctx_merge(cb, GMX_CTX_WAVE_ROUTE_MIXER, t.m, vals, contexts, xcm);
+    if (mb) {
+      chain_ctx_merge(cb, GMX_CTX_WAVE_ROUTE_MATCH, KM, vals, match_contexts, mcm);
+      rc = gmx_chain_forward_match(ib, g, stream, icm, mcm, bc, predictions, active_models, n_active, xcm, p_final,
+                                   out_all, ip_, ia_, mp_, ma_, &lm);
+    } else {
+      rc = gmx_chain_forward(ib, g, stream, icm, bc, predictions, active_models, n_active, xcm, p_final, out_all, ip_, ia_);
+    }
+    if (rc == GMX_OK && ctx_values) memcpy(ctx_values, vals, 4 * (size_t)cb->dev.v);
+  }
+  if (rc) return rc;
+  if (ind_predictions) memcpy(ind_predictions, ip_, (size_t)2 * K * 4);
+  if (ind_active) memcpy(ind_active, ia_, (size_t)2 * K);
+  if (mb) {
+    if (match_predictions) memcpy(match_predictions, mp_, (size_t)KM * 4);
+    if (match_active) memcpy(match_active, ma_, (size_t)KM);
+    if (longest_match) *longest_match = lm;
+  }
+  if (bit_context) *bit_context = bc;
   return GMX_OK;
 }
 

@@ -695,7 +695,12 @@ extern "C" int gmx_chainstep_attach_ctx(gmx_chainstep* cs, gmx_ctx* cb, const gm
     if (routes->mixer_route[c] >= 0 && device_owned_mixer(c)) return GMX_ERR_INVALID;
   if (has_ind && cs->ind_ctx_col >= 0 && routes->ind_route[cs->ind_ctx_col] >= 0) return GMX_ERR_INVALID;
   if (cb->chainstep) return GMX_ERR_STATE;  // one lock-step object per bank
+  if (cb->host) return GMX_ERR_STATE;       // (its streams ride in per-bit session waves: gmx_indirect_attach_ctx)
   HIPCHK(hipSetDevice(g->device));
+  for (int s = 0; s < cb->S && cb->n_noted > 0; ++s) {  // a learn gmx_ctx_learn noted: the boards are read below
+    const int rcn = ctx_flush_noted(cb, s);
+    if (rcn) return rcn;
+  }
   HIPCHK(hipStreamSynchronize(cb->stream));
   HIPCHK(hipStreamSynchronize(g->stream));
   const GmxStepUpload up_before = cs->up;

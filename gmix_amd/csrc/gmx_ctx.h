@@ -101,6 +101,41 @@ struct GmxCtxStepArgs {
   GmxCtxTarget tg[3];       // mixers, Indirect, Match: ctx [S][n_cols] (stride, bc, bits unused)
 };
 
+// One bit of ONE stream on the launch path (gmx_ctx_forward / gmx_ctx_learn, gmx_ctx_bit_kernel): what the stream asks
+// and the bit a Learn takes are kernel arguments; the answer goes into a small pinned block.
+struct GmxCtxBitReply {
+  uint32_t bit_context;
+  uint32_t pad[15];
+  uint32_t values[GMX_CTX_MAX_VARS];
+};
+struct GmxCtxBitArgs {
+  uint8_t* banks;
+  GmxCtxBitReply* reply;    // pinned host memory
+  int32_t stream;
+  uint32_t what;            // GMX_CTX_STEP_LEARN | GMX_CTX_STEP_PREDICT
+  uint32_t bit;
+  uint32_t pad;
+};
+
+// The stream's context variables riding in the per-bit session wave of the Indirect models (gmx_indirect_attach_ctx,
+// gmx_ctx_step_wave in gmx_ctx_step.h).  What they do in a chained forward is the command's ctx_what word:
+// GMX_CTX_STEP_LEARN | GMX_CTX_STEP_PREDICT, and
+#define GMX_CTX_WAVE_VALUES 4u     // the V values go into the reply as well
+#define GMX_CTX_WAVE_RELOAD 8u     // something else has moved the stream's board since the wave's last step: its register
+                                   // copy is read again
+#define GMX_CTX_WAVE_BIT_SHIFT 8   // the coded bit of the Learn
+struct GmxCtxWaveArgs {
+  const GmxCtxDev* dev;     // null: no context bank rides
+  uint8_t* bank;            // the STREAM's bank
+  const int32_t* routes;    // device memory: [64] Indirect columns | [8] Match columns | [64] mixer columns; -1: not routed
+  int32_t n_mixer_cols;
+  int32_t pad;
+};
+#define GMX_CTX_WAVE_ROUTE_IND 0
+#define GMX_CTX_WAVE_ROUTE_MATCH 64
+#define GMX_CTX_WAVE_ROUTE_MIXER 72
+#define GMX_CTX_WAVE_ROUTE_WORDS 136
+
 // ---- checkpoint (indirect-hash.cpp:33-54): tables walked in chunks, one block per chunk
 #define GMX_CTX_CKPT_CHUNK 16384
 struct GmxCtxCkptChunk {

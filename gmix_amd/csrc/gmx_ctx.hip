@@ -12,7 +12,8 @@
 //   gmx_ctx_commit_kernel  the board for the run's end (ring, recent_bits, values): a launch of its own because every
 //                          block of the expand kernel reads the board of the run's beginning
 // In the lock-step chain (gmx_chainstep_attach_ctx) a coded bit is one launch instead: gmx_ctx_step_kernel, a wave per
-// stream around gmx_ctx_step.h, which leaves the board and the tables as a run over the same bits does.
+// stream around gmx_ctx_step.h, which leaves the board and the tables as a run over the same bits does; the per-bit
+// surface (gmx_ctx_forward / gmx_ctx_learn) is the same step for one stream, gmx_ctx_bit_kernel.
 //
 // Geometry of a run.  The board holds recent_bits as of the stream's newest Predict and new_bit, the bit coded since
 // (basic-contexts.cpp:28-34 runs at the NEXT Predict).  p = 2 recent_bits + new_bit is what record 0 sees before the
@@ -263,6 +264,17 @@ __global__ __launch_bounds__(64) void gmx_ctx_step_kernel(const GmxCtxDev* __res
   gmx_ctx_step_body(dv, a, (int)blockIdx.x, (int)threadIdx.x, stage);
 }
 
+// ---- one bit of ONE stream on the launch path (gmx_ctx_forward / gmx_ctx_learn): the same step, a block of one wave;
+// what the stream asks and the bit come in as kernel arguments, the V values and bit_context go into a pinned reply
+__global__ __launch_bounds__(64) void gmx_ctx_bit_kernel(const GmxCtxDev* __restrict__ dv, GmxCtxBitArgs a) {
+  __shared__ uint32_t stage[GMX_CTX_MAX_VARS];
+  const int lane = (int)threadIdx.x;
+  if (!(a.what & (GMX_CTX_STEP_LEARN | GMX_CTX_STEP_PREDICT))) return;
+  gmx_ctx_step_core(dv, a.banks + (size_t)a.stream * dv->bank_bytes, a.what, a.bit & 1u, lane, stage, nullptr, 0,
+                    &a.reply->bit_context);
+  if ((a.what & GMX_CTX_STEP_PREDICT) && lane < dv->v) a.reply->values[lane] = stage[lane];
+}
+
 // recent_bits, new_bit and first_prediction of every stream, gathered for one transfer (gmx_chainstep_attach_ctx)
 __global__ void gmx_ctx_heads_kernel(const GmxCtxDev* __restrict__ dv, const uint8_t* banks, int n_streams, uint32_t* out) {
   const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -364,6 +376,12 @@ extern "C" hipError_t gmx_launch_ctx_run(const GmxCtxDev* dv, int n_hash, const 
 extern "C" hipError_t gmx_launch_ctx_step(const GmxCtxDev* dv, const GmxCtxStepArgs* args, hipStream_t stream) {
   (void)hipGetLastError();
   hipLaunchKernelGGL(gmx_ctx_step_kernel, dim3((unsigned)args->n_streams), dim3(64), 0, stream, dv, *args);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t gmx_launch_ctx_bit(const GmxCtxDev* dv, const GmxCtxBitArgs* args, hipStream_t stream) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gmx_ctx_bit_kernel, dim3(1), dim3(64), 0, stream, dv, *args);
   return hipGetLastError();
 }
 

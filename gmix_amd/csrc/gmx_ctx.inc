@@ -46,15 +46,51 @@ struct gmx_ctx {
   std::vector<uint8_t> outstanding;
   struct GmxCtxGckState* gck = nullptr;  // the group checkpoint's staging, lazily (gmx_ctx_ckpt.inc)
   int gck_ops = 0;                       // round trips of the newest group call (gmx_debug_ctx_group_ops)
+  // The per-bit surface (gmx_ctx_forward / gmx_ctx_learn).  A learn is only noted (1 + bit) and travels with the
+  // stream's next forward -- a launch, or a command of the session wave the stream rides in; `outstanding` above is
+  // "a forward waits for its learn" here as well.
+  std::vector<uint8_t> noted;
+  int n_noted = 0;
+  GmxCtxBitReply* bit_reply = nullptr;   // pinned, lazily
+  int bit_launches = 0;                  // launches of gmx_ctx_bit_kernel so far (gmx_debug_ctx_bit_launches)
+  // gmx_indirect_attach_ctx: the streams step at the head of a chained forward in the session waves of `host`.
+  // wave_fresh[s]: the register copy of stream s's wave, if one runs, is what the board holds -- nothing but that
+  // wave has moved the stream since; otherwise its next command says GMX_CTX_WAVE_RELOAD.
+  gmx_indirect* host = nullptr;
+  int32_t* routes_d = nullptr;
+  int32_t routes[GMX_CTX_WAVE_ROUTE_WORDS] = {};
+  bool own_ind = false, own_match = false;  // a column of the Indirect / Match records is the caller's (routed -1)
+  std::vector<uint8_t> wave_fresh;
 };
 static void ctx_gck_free(gmx_ctx* cb);  // gmx_ctx_ckpt.inc
 static void chainstep_ctx_gone(gmx_chainstep* cs);  // gmx_chainstep.inc
 static int chainstep_settle(gmx_chainstep* cs);     // ... no step of it is in flight any more
+static int ctx_flush_noted(gmx_ctx* cb, int s);
 
-// Before a gmx_ctx_* call reads or writes an attached bank: the lock-step object's steps run on the group's stream.
-static int ctx_settle(gmx_ctx* cb) { return cb->chainstep ? chainstep_settle(cb->chainstep) : GMX_OK; }
+// Before a gmx_ctx_* call reads or writes the bank through anything but the per-bit surface: the steps of a lock-step
+// object it is attached to run on the group's stream; the session waves it rides in stop (they keep nothing of a
+// stream's state, so there is nothing to write back), and every noted learn is run.
+static int ctx_settle(gmx_ctx* cb) {
+  int first = cb->chainstep ? chainstep_settle(cb->chainstep) : GMX_OK;
+  if (cb->host) {
+    const int rc = ind_sessions_close(cb->host);
+    if (rc && !first) first = rc;
+    std::fill(cb->wave_fresh.begin(), cb->wave_fresh.end(), 0);
+  }
+  for (int s = 0; s < cb->S && cb->n_noted > 0; ++s) {
+    const int rc = ctx_flush_noted(cb, s);
+    if (rc && !first) first = rc;
+  }
+  return first;
+}
+
+// Before stream s's board is moved by anything but a command of the wave the stream rides in (s < 0: every stream): see
+// ind_ctx_board_moves.  An Indirect forward that took its indices from the board is learned now if its learn is noted,
+// and void otherwise.
+static int ctx_board_moves(gmx_ctx* cb, int s) { return cb->host ? ind_ctx_board_moves(cb->host, s) : GMX_OK; }
 
 extern "C" {
+hipError_t gmx_launch_ctx_bit(const GmxCtxDev* dv, const GmxCtxBitArgs* args, hipStream_t stream);
 hipError_t gmx_launch_ctx_run(const GmxCtxDev* dv, int n_hash, const GmxCtxRunArgs* args, hipStream_t stream,
                               hipEvent_t* marks);
 hipError_t gmx_launch_ctx_init(const GmxCtxDev* dv, uint8_t* banks, int n_streams, hipStream_t stream);
@@ -88,7 +124,10 @@ extern "C" void gmx_ctx_destroy(gmx_ctx* cb) {
   (void)hipSetDevice(cb->device);
   if (cb->chainstep) chainstep_ctx_gone(cb->chainstep);  // (its later steps fail; none is in flight any more)
   cb->chainstep = nullptr;
+  if (cb->host) (void)ctx_host_detach(cb);  // (the waves stop: none of them holds this bank any more)
   if (cb->stream) (void)hipStreamSynchronize(cb->stream);
+  if (cb->routes_d) (void)hipFree(cb->routes_d);
+  if (cb->bit_reply) (void)hipHostFree(cb->bit_reply);
   for (gmx_ctx_batch* b : cb->batches) b->cb = nullptr;  // shells, as for gmx_batch
   cb->batches.clear();
   void* dv[] = {cb->banks, cb->dev_d, cb->chunks_d, cb->chunk_cnt_d, cb->chunk_base_d, cb->hash_dense_d,
@@ -109,10 +148,13 @@ extern "C" int gmx_ctx_reset(gmx_ctx* cb) {
   if (!cb) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(cb->device));
   {
-    int rcs = ctx_settle(cb);
+    int rcs = ctx_board_moves(cb, -1);
+    if (!rcs) rcs = ctx_settle(cb);
     if (rcs) return rcs;
   }
   std::fill(cb->outstanding.begin(), cb->outstanding.end(), 0);
+  std::fill(cb->noted.begin(), cb->noted.end(), 0);
+  cb->n_noted = 0;
   cb->moved = true;
   HIPCHK(hipMemsetAsync(cb->banks, 0, (size_t)cb->S * cb->dev.bank_bytes, cb->stream));
   HIPCHK(gmx_launch_ctx_init(cb->dev_d, cb->banks, cb->S, cb->stream));
@@ -211,6 +253,8 @@ extern "C" int gmx_ctx_create(gmx_ctx** out, const gmx_ctx_desc* descs, int n_va
   cb->device = device;
   cb->S = n_streams;
   cb->outstanding.assign((size_t)n_streams, 0);
+  cb->noted.assign((size_t)n_streams, 0);
+  cb->wave_fresh.assign((size_t)n_streams, 0);
   const GmxCtxDev& d = cb->dev;
   for (int i = 0; i < d.h; ++i)
     for (uint32_t e = 0; e < d.hash[i].table_size; e += GMX_CTX_CKPT_CHUNK) {
@@ -472,7 +516,8 @@ extern "C" int gmx_ctx_run(gmx_ctx* cb, gmx_ctx_batch* b, uint64_t n_bits, const
     for (int s = 0; s < cb->S; ++s)
       if (cb->outstanding[s]) return GMX_ERR_STATE;
   HIPCHK(hipSetDevice(cb->device));
-  rc = ctx_settle(cb);
+  rc = n_bits ? ctx_board_moves(cb, -1) : GMX_OK;
+  if (!rc) rc = ctx_settle(cb);
   if (rc) return rc;
   if (kernel_ms) *kernel_ms = 0.0f;
   cb->moved = true;
@@ -499,10 +544,100 @@ extern "C" int gmx_ctx_run_ragged(gmx_ctx* cb, gmx_ctx_batch* b, const uint64_t*
   int rc = ctx_targets_ok(cb, targets, maxn);
   if (rc) return rc;
   HIPCHK(hipSetDevice(cb->device));
-  rc = ctx_settle(cb);
+  for (int s = 0; s < cb->S && !rc; ++s)
+    if (n_bits[s]) rc = ctx_board_moves(cb, s);
+  if (!rc) rc = ctx_settle(cb);
   if (rc) return rc;
   cb->moved = true;
   return ctx_launch(cb, b, maxn, same ? nullptr : n_bits, targets, nullptr);
+}
+
+// ---- the per-bit surface: one record of gmx_ctx_run for one stream -----------------------------------------
+// One launch of gmx_ctx_bit_kernel on the bank's stream, waited for when it predicts.  The stream's wave, if one runs
+// (gmx_indirect_attach_ctx), does not touch the context bank unless a command tells it to, and every store of its
+// last command was in memory before the host saw the answer: it need not stop, but it reads its copy again.
+static int ctx_bit_launch(gmx_ctx* cb, int stream, uint32_t what, uint32_t bit, uint32_t* values, uint32_t* bit_context) {
+  if (!cb->bit_reply) {
+    HIPCHK(hipHostMalloc((void**)&cb->bit_reply, sizeof(GmxCtxBitReply), hipHostMallocDefault));
+    memset(cb->bit_reply, 0, sizeof(GmxCtxBitReply));
+  }
+  GmxCtxBitArgs a;
+  memset(&a, 0, sizeof a);
+  a.banks = cb->banks;
+  a.reply = cb->bit_reply;
+  a.stream = stream;
+  a.what = what;
+  a.bit = bit;
+  HIPCHK(gmx_launch_ctx_bit(cb->dev_d, &a, cb->stream));
+  cb->bit_launches += 1;
+  if (cb->host) cb->wave_fresh[stream] = 0;
+  cb->moved = true;
+  if (!(what & GMX_STEP_PREDICT)) return GMX_OK;  // (a learn is not waited for: whatever reads the bank next is behind it)
+  HIPCHK(hipStreamSynchronize(cb->stream));
+  if (values) memcpy(values, cb->bit_reply->values, 4 * (size_t)cb->dev.v);
+  if (bit_context) *bit_context = cb->bit_reply->bit_context;
+  return GMX_OK;
+}
+
+// A learn gmx_ctx_learn noted for stream s: on its own through the launch path now.
+static int ctx_flush_noted(gmx_ctx* cb, int s) {
+  if (!cb->noted[s]) return GMX_OK;
+  const int rc = ctx_bit_launch(cb, s, GMX_STEP_LEARN, (uint32_t)(cb->noted[s] - 1), nullptr, nullptr);
+  if (rc) return rc;
+  cb->noted[s] = 0;
+  cb->n_noted -= 1;
+  return GMX_OK;
+}
+
+// The forward on the launch path; a noted learn of the stream travels in the same launch.
+static int ctx_forward_launch(gmx_ctx* cb, int stream, uint32_t* values, uint32_t* bit_context) {
+  {
+    // (the Indirect learn of the stream's last chained forward first, where it is only noted: a wave restarted for it
+    // later would recompute that forward from the board this launch moves)
+    const int rcm = ctx_board_moves(cb, stream);
+    if (rcm) return rcm;
+  }
+  uint32_t what = GMX_STEP_PREDICT, bit = 0;
+  if (cb->noted[stream]) {
+    what |= GMX_STEP_LEARN;
+    bit = (uint32_t)(cb->noted[stream] - 1);
+  }
+  const int rc = ctx_bit_launch(cb, stream, what, bit, values, bit_context);
+  if (rc) return rc;
+  if (cb->noted[stream]) {
+    cb->noted[stream] = 0;
+    cb->n_noted -= 1;
+  }
+  cb->outstanding[stream] = 1;
+  return GMX_OK;
+}
+
+// Tests: launches of gmx_ctx_bit_kernel on this bank so far -- forwards and learns of the launch path; a bit that went
+// through the session wave adds none.
+extern "C" int gmx_debug_ctx_bit_launches(const gmx_ctx* cb) { return cb ? cb->bit_launches : GMX_ERR_INVALID; }
+
+extern "C" int gmx_ctx_forward(gmx_ctx* cb, int stream, uint32_t* values, uint32_t* bit_context) {
+  if (!cb || stream < 0 || stream >= cb->S) return GMX_ERR_INVALID;
+  if (cb->chainstep) return GMX_ERR_STATE;            // the lock-step object steps this bank
+  if (cb->outstanding[stream]) return GMX_ERR_STATE;  // a Predict moves state: one per bit
+  HIPCHK(hipSetDevice(cb->device));
+  if (cb->host) {  // the waves stop; the stream's own noted learn still travels with this forward
+    const int rc = ind_sessions_close(cb->host);
+    if (rc) return rc;
+    std::fill(cb->wave_fresh.begin(), cb->wave_fresh.end(), 0);
+  }
+  return ctx_forward_launch(cb, stream, values, bit_context);
+}
+
+// ShortTermMemory::new_bit of the stream: what Predictor::Learn and Predictor::Perceive both leave for the next
+// BasicContexts::Predict, so a generated bit is perceived through this call too.
+extern "C" int gmx_ctx_learn(gmx_ctx* cb, int stream, int bit) {
+  if (!cb || stream < 0 || stream >= cb->S || (bit != 0 && bit != 1)) return GMX_ERR_INVALID;
+  if (cb->chainstep) return GMX_ERR_STATE;
+  if (!cb->noted[stream]) cb->n_noted += 1;
+  cb->noted[stream] = (uint8_t)(1 + bit);
+  cb->outstanding[stream] = 0;
+  return GMX_OK;
 }
 
 // ---- the blackboard --------------------------------------------------------------------------------
@@ -550,7 +685,8 @@ extern "C" int gmx_ctx_blackboard_set(gmx_ctx* cb, int stream, const gmx_ctx_bla
   memcpy(bd.values, in->values, 4 * (size_t)cb->dev.v);
   HIPCHK(hipSetDevice(cb->device));
   {
-    int rcs = ctx_settle(cb);
+    int rcs = ctx_board_moves(cb, stream);
+    if (!rcs) rcs = ctx_settle(cb);
     if (rcs) return rcs;
   }
   HIPCHK(hipStreamSynchronize(cb->stream));
@@ -825,7 +961,8 @@ extern "C" int gmx_ctx_copy(gmx_ctx* dst, int dst_stream, gmx_ctx* src, int src_
   if (dst == src && dst_stream == src_stream) return GMX_OK;
   HIPCHK(hipSetDevice(src->device));
   {
-    int rcs = ctx_settle(src);
+    int rcs = ctx_board_moves(dst, dst_stream);
+    if (!rcs) rcs = ctx_settle(src);
     if (!rcs && dst != src) rcs = ctx_settle(dst);
     if (rcs) return rcs;
   }
@@ -847,5 +984,72 @@ extern "C" int gmx_ctx_memory_usage(gmx_ctx* cb, int var, uint64_t* bytes) {
            : v.kind == GMX_CTX_INTERVAL    ? 256ull * 4 + 8 + 4
            : v.kind == GMX_CTX_SKIP        ? 4ull * (uint64_t)v.n_bytes + 4
                                            : 0;
+  return GMX_OK;
+}
+
+// ---- in the per-bit sessions: the bank's streams step in the session waves of an Indirect bank -----------------------
+// Either object goes, or the attachment is given up: the waves stop (nothing of a stream's context state lives in
+// them), a noted learn stays noted and takes the launch path with the stream's next forward.
+static int ctx_host_detach(gmx_ctx* cb) {
+  if (!cb || !cb->host) return GMX_OK;
+  gmx_indirect* ib = cb->host;
+  (void)hipSetDevice(ib->device);
+  const int rc = ind_sessions_close(ib);
+  ib->ctx = nullptr;
+  ib->ctx_dev_d = nullptr;
+  ib->ctx_banks = nullptr;
+  ib->ctx_routes_d = nullptr;
+  ib->ctx_bank_bytes = 0;
+  ib->ctx_v = ib->ctx_n_mixer_cols = 0;
+  cb->host = nullptr;
+  std::fill(cb->wave_fresh.begin(), cb->wave_fresh.end(), 0);
+  return rc;
+}
+
+extern "C" int gmx_indirect_attach_ctx(gmx_indirect* ib, gmx_ctx* cb, const gmx_ctx_step_routes* routes) {
+  if (!ib) return GMX_ERR_INVALID;
+  if (!cb) {  // detach
+    HIPCHK(hipSetDevice(ib->device));
+    return ib->ctx ? ctx_host_detach(ib->ctx) : GMX_OK;
+  }
+  if (!routes || cb->S != ib->S || cb->device != ib->device) return GMX_ERR_INVALID;
+  const int K = ib->dev.k, KM = ib->match ? ib->match_k : 0;
+  // (the mixer route's length is checked against the group's M by the forward, which knows the group)
+  if (routes->n_mixer_route > GMX_MAX_MIXERS ||
+      ctx_route_ok(cb, routes->mixer_route, routes->n_mixer_route, routes->n_mixer_route))
+    return GMX_ERR_INVALID;
+  if (ctx_route_ok(cb, routes->ind_route, routes->n_ind_route, K)) return GMX_ERR_INVALID;
+  const bool has_match = routes->match_route || routes->n_match_route;
+  if (has_match != (KM > 0)) return GMX_ERR_INVALID;  // NULL / 0 iff no Match bank is attached to ib
+  if (has_match && ctx_route_ok(cb, routes->match_route, routes->n_match_route, KM)) return GMX_ERR_INVALID;
+  for (int c = 0; c < ib->match_n_cols; ++c)  // a column has one writer on the device
+    if (KM > 0 && ib->match_cols[c] < routes->n_mixer_route && routes->mixer_route[ib->match_cols[c]] >= 0)
+      return GMX_ERR_INVALID;
+  if (cb->chainstep) return GMX_ERR_STATE;  // one host of its per-bit state at a time
+  if (cb->host && cb->host != ib) return GMX_ERR_STATE;
+  HIPCHK(hipSetDevice(ib->device));
+  int rc = ib->ctx ? ctx_host_detach(ib->ctx) : GMX_OK;  // (another bank, or this one with other routes)
+  if (rc) return rc;
+  rc = ind_sessions_close(ib);  // the waves that run are a build without the context phase
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(cb->stream));
+  if (!cb->routes_d) HIPCHK(hipMalloc((void**)&cb->routes_d, sizeof cb->routes));
+  for (int32_t& r : cb->routes) r = -1;
+  memcpy(cb->routes + GMX_CTX_WAVE_ROUTE_IND, routes->ind_route, 4 * (size_t)K);
+  if (has_match) memcpy(cb->routes + GMX_CTX_WAVE_ROUTE_MATCH, routes->match_route, 4 * (size_t)KM);
+  memcpy(cb->routes + GMX_CTX_WAVE_ROUTE_MIXER, routes->mixer_route, 4 * (size_t)routes->n_mixer_route);
+  HIPCHK(hipMemcpy(cb->routes_d, cb->routes, sizeof cb->routes, hipMemcpyHostToDevice));
+  cb->own_ind = cb->own_match = false;
+  for (int c = 0; c < K; ++c) cb->own_ind = cb->own_ind || routes->ind_route[c] < 0;
+  for (int c = 0; c < KM; ++c) cb->own_match = cb->own_match || routes->match_route[c] < 0;
+  std::fill(cb->wave_fresh.begin(), cb->wave_fresh.end(), 0);
+  ib->ctx = cb;
+  ib->ctx_dev_d = cb->dev_d;
+  ib->ctx_banks = cb->banks;
+  ib->ctx_bank_bytes = cb->dev.bank_bytes;
+  ib->ctx_routes_d = cb->routes_d;
+  ib->ctx_v = cb->dev.v;
+  ib->ctx_n_mixer_cols = routes->n_mixer_route;
+  cb->host = ib;
   return GMX_OK;
 }

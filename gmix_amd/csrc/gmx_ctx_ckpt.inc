@@ -318,7 +318,9 @@ extern "C" int gmx_ctx_group_blackboard_set(gmx_ctx* cb, int first, int count, c
   cb->gck_ops = 0;
   HIPCHK(hipSetDevice(cb->device));
   {
-    int rcs = ctx_settle(cb);
+    int rcs = GMX_OK;
+    for (int s = first; s < first + count && !rcs; ++s) rcs = ctx_board_moves(cb, s);
+    if (!rcs) rcs = ctx_settle(cb);
     if (rcs) return rcs;
   }
   GmxCtxGckState* c = nullptr;

@@ -19,6 +19,7 @@
 
 #include <type_traits>
 
+#include "gmx_ctx_step.h"
 #include "gmx_internal.h"
 #include "gmx_match_step.h"
 #include "gmx_math.h"
@@ -490,11 +491,28 @@ extern "C" hipError_t gmx_launch_indirect_kernel(const GmxIndDev* dv, const GmxI
 // poll, which invalidates L1: no load of command n+1 can be served from a line older than the stores of command n.
 // Inside a command nothing is read back from memory: the hand-overs go through registers (gmx_match_step.h).
 // ---------------------------------------------------------------------------------------
-template <bool WITH_MATCH>
+//
+// WITH_CTX (gmx_indirect_attach_ctx): the stream's context variables (gmx_ctx_step_wave in gmx_ctx_step.h) step in the
+// SAME wave, as a phase at the head of a chained forward: lane v < V holds variable v for that phase, and is an
+// Indirect / Match lane again afterwards.  What the phase does is the payload slot's ctx_what (gmx_ctx.h).  The V
+// values are staged in 256 bytes of LDS beside the four mask words; the Indirect lanes take their context from there
+// where their column is routed (the mailbox word otherwise), the Match lanes their context word and bit_context (the
+// two fields of GmxMatchStepLane are overwritten between `begin` and `fetch`: gmx_match_step.h is as it was), and the
+// mixers' routed gate contexts are stored into their payload before their doorbell is rung.  Nothing is written into
+// this wave's own command mailbox.
+//   The wave keeps a write-through copy of the board's small state in registers (GmxCtxWaveCopy): a bit that opens no
+// byte loads nothing from the context bank.  Every change is stored to the bank before the command's closing
+// s_waitcnt vmcnt(0), so the argument above holds for the context state as it does for the Match state: nothing of it
+// lives outside the bank once a command is answered -- an idle exit, an eviction and a stop have nothing to write
+// back -- and what a lane reads back at a later byte opening (the ring bytes lane 0 stored, its own table entry and
+// hash state) it reads behind the acquire fence of a later command.  A replayed forward does NOT step the bank again:
+// the board holds the full values of that Predict (gmx_ctx_step_wave_replay).  When another surface has moved the
+// stream since the wave's last step the host says so in ctx_what (GMX_CTX_WAVE_RELOAD) and the copy is read again.
+template <bool WITH_MATCH, bool WITH_CTX>
 __global__ void __launch_bounds__(64)
 gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, int stream, GmxIndMbCmd* mc,
                             GmxIndMbReply* mr, unsigned long long idle_ticks, int replay_forward,
-                            const GmxMatchDev* __restrict__ mdv, const GmxMatchStepArgs ma0) {
+                            const GmxMatchDev* __restrict__ mdv, const GmxMatchStepArgs ma0, const GmxCtxWaveArgs ca) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x;
   const int K = dv->k;
@@ -527,6 +545,25 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
   bool have_fwd = false, dirty = false;
   bool replay = replay_forward != 0;
   uint32_t exit_state = GMX_MB_EXIT_IDLE;
+  // WITH_CTX: the stage behind the mask words' 64 bytes, the lane's variable and routes, the register copy of the board
+  uint32_t* const cstage = (uint32_t*)(rmn + 512) + 16;
+  GmxCtxBoard* cbd = nullptr;
+  GmxCtxWaveCopy cc;
+  cc.rb = cc.nb = cc.fp = cc.pos = cc.base = 0;
+  cc.loaded = false;
+  int cV = 0, ckind = GMX_CTXK_ZERO, cindex = 0;
+  int32_t r_ind = -1, r_match = -1, r_mix = -1;
+  if (WITH_CTX) {
+    cV = ca.dev->v;
+    cbd = (GmxCtxBoard*)(ca.bank + ca.dev->board_off);
+    if (lane < cV) {
+      ckind = ca.dev->var[lane].kind;
+      cindex = ca.dev->var[lane].index;
+    }
+    r_ind = ca.routes[GMX_CTX_WAVE_ROUTE_IND + ml];
+    if (lane >= 56) r_match = ca.routes[GMX_CTX_WAVE_ROUTE_MATCH + lane - 56];
+    if (lane < ca.n_mixer_cols) r_mix = ca.routes[GMX_CTX_WAVE_ROUTE_MIXER + lane];
+  }
   for (;;) {
     uint32_t word = seen, cmd = GMX_MB_FORWARD;
     uint32_t slot = (uint32_t)(replay_forward - 1) & 1u;
@@ -548,6 +585,19 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
     const bool with_learn = cmd == GMX_MB_LEARN0 || cmd == GMX_MB_LEARN1 || cmd == GMX_MB_LEARN0_FWD ||
                             cmd == GMX_MB_LEARN1_FWD;
     const bool with_forward = cmd == GMX_MB_FORWARD || cmd == GMX_MB_LEARN0_FWD || cmd == GMX_MB_LEARN1_FWD;
+    // ---- the context variables' phase: before the Match lanes' first trip and the Indirect models' index computation,
+    // which consume its values (a replayed forward reads them back from the board instead)
+    uint32_t cwhat = 0, cbc = 0;
+    if (WITH_CTX) {
+      if (with_forward) cwhat = __builtin_amdgcn_readfirstlane(vc->ctx_what[slot]) & 0x10fu;
+      if (!(cwhat & GMX_CTX_STEP_PREDICT)) cwhat = 0;  // (the host sends a Learn only with its stream's next Predict)
+      if (cwhat) {  // (wave-uniform)
+        cbc = replay ? gmx_ctx_step_wave_replay(cbd, cV, lane, cstage)
+                     : gmx_ctx_step_wave(ca.dev, ca.bank, cbd, cV, ckind, cindex, cc, lane, cwhat, cstage);
+        cbc = __builtin_amdgcn_readfirstlane(cbc);
+        __syncthreads();  // the values are staged
+      }
+    }
     // ---- the Match lanes' trip 1, beside the rest of the mailbox read (a replayed forward: they sit it out)
     GmxMatchStepLane mt;
     // (the step's arguments, field by field, and without the column list: a local copy that the step indexes by a
@@ -573,6 +623,10 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
         ma.bits = (const uint8_t*)&mc->match_what[slot] + 1;  // bit 8 of the word
         ma.mx_pred = mp->pred;
         gmx_match_step_begin(mt, mdv, ma, 0, lane - 56, lane >= 56, mwhat);
+        if (WITH_CTX && cwhat) {  // this step's record is the bank's: bit_context, and the routed context words
+          mt.bc = cbc;
+          if (r_match >= 0) mt.rctx = cstage[r_match];
+        }
       }
     }
     if (with_learn && have_fwd) {
@@ -592,8 +646,12 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
     }
     if (with_forward) {
       // ---- Indirect::Predict (indirect.cpp:28-46) -------------------------------------------
-      const uint32_t ctx = vc->ctx[slot][ml];
-      const uint32_t bcu = vc->bit_context[slot];
+      uint32_t ctx = vc->ctx[slot][ml];
+      uint32_t bcu = vc->bit_context[slot];
+      if (WITH_CTX && cwhat) {
+        if (r_ind >= 0) ctx = cstage[r_ind];
+        bcu = cbc;
+      }
       idx = ((ctx << 8) + bcu) % d.size;  // indirect.cpp:31-32, 32-bit wrap
       uint32_t ev;
       if (WITH_MATCH && (mwhat & 3u)) {
@@ -650,6 +708,12 @@ gmx_indirect_session_kernel(const GmxIndDev* __restrict__ dv, uint8_t* banks, in
               }
             }
           }
+          if (WITH_CTX && cwhat) {
+            // the mixers' routed gate contexts, lanes along the columns; bit_context and, if asked for, the V values
+            if (r_mix >= 0) mp->ctx[lane] = cstage[r_mix];
+            if (lane == 0) vr->ctx_bit_context = cbc;
+            if ((cwhat & GMX_CTX_WAVE_VALUES) && lane < cV) vr->ctx_values[lane] = cstage[lane];
+          }
           if (lane < 4) mp->mask[lane] = mp->mask[lane] | mwl[lane];  // the host left these bits clear
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
@@ -689,15 +753,17 @@ extern "C" hipError_t gmx_launch_indirect_session(const GmxIndDev* dv, uint8_t* 
   (void)hipGetLastError();
   static unsigned allowed = 48u * 1024u;
   if (lds_bytes > allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel<false>,
+    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel<false, false>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
     allowed = lds_bytes;
   }
   GmxMatchStepArgs mnone;
   memset(&mnone, 0, sizeof mnone);
-  hipLaunchKernelGGL(gmx_indirect_session_kernel<false>, dim3(1), dim3(64), lds_bytes, stream, dv, banks, stream_idx,
-                     mc, mr, idle_ticks, replay_forward, (const GmxMatchDev*)nullptr, mnone);
+  GmxCtxWaveArgs cnone;
+  memset(&cnone, 0, sizeof cnone);
+  hipLaunchKernelGGL((gmx_indirect_session_kernel<false, false>), dim3(1), dim3(64), lds_bytes, stream, dv, banks,
+                     stream_idx, mc, mr, idle_ticks, replay_forward, (const GmxMatchDev*)nullptr, mnone, cnone);
   return hipGetLastError();
 }
 // ... with the stream's Match models in lanes 56..63: margs->banks / hist are the STREAM's (the wave steps them as
@@ -714,13 +780,50 @@ extern "C" hipError_t gmx_launch_indirect_session_match(const GmxIndDev* dv, int
     return hipErrorInvalidValue;
   static unsigned allowed = 48u * 1024u;
   if (lds_bytes > allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel<true>,
+    hipError_t e = hipFuncSetAttribute((const void*)gmx_indirect_session_kernel<true, false>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
     allowed = lds_bytes;
   }
-  hipLaunchKernelGGL(gmx_indirect_session_kernel<true>, dim3(1), dim3(64), lds_bytes, stream, dv, banks, stream_idx,
-                     mc, mr, idle_ticks, replay_forward, mdv, *margs);
+  GmxCtxWaveArgs cnone;
+  memset(&cnone, 0, sizeof cnone);
+  hipLaunchKernelGGL((gmx_indirect_session_kernel<true, false>), dim3(1), dim3(64), lds_bytes, stream, dv, banks,
+                     stream_idx, mc, mr, idle_ticks, replay_forward, mdv, *margs, cnone);
+  return hipGetLastError();
+}
+
+// ... with the stream's context variables stepping at the head of a chained forward (gmx_indirect_attach_ctx), and
+// with the Match models too when mdv is not null.  cargs->bank is the STREAM's context bank; lds_bytes includes the 256
+// bytes of the stage behind the mask words.
+extern "C" hipError_t gmx_launch_indirect_session_ctx(const GmxIndDev* dv, int k_ind, uint8_t* banks, int stream_idx,
+                                                      GmxIndMbCmd* mc, GmxIndMbReply* mr, unsigned long long idle_ticks,
+                                                      int replay_forward, const GmxMatchDev* mdv,
+                                                      const GmxMatchStepArgs* margs, const GmxCtxWaveArgs* cargs,
+                                                      unsigned lds_bytes, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!cargs || !cargs->dev || !cargs->bank || !cargs->routes || cargs->n_mixer_cols < 0 || cargs->n_mixer_cols > 64)
+    return hipErrorInvalidValue;
+  if (mdv && (k_ind > 56 || !margs || !margs->banks || !margs->hist || margs->n_ctx_cols < 0 ||
+              margs->n_ctx_cols > GMX_MATCH_MAX_CTX_COLS))
+    return hipErrorInvalidValue;
+  static unsigned allowed[2] = {48u * 1024u, 48u * 1024u};
+  const int w = mdv ? 1 : 0;
+  if (lds_bytes > allowed[w]) {
+    hipError_t e = hipFuncSetAttribute(mdv ? (const void*)gmx_indirect_session_kernel<true, true>
+                                           : (const void*)gmx_indirect_session_kernel<false, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    allowed[w] = lds_bytes;
+  }
+  if (mdv) {
+    hipLaunchKernelGGL((gmx_indirect_session_kernel<true, true>), dim3(1), dim3(64), lds_bytes, stream, dv, banks,
+                       stream_idx, mc, mr, idle_ticks, replay_forward, mdv, *margs, *cargs);
+  } else {
+    GmxMatchStepArgs mnone;
+    memset(&mnone, 0, sizeof mnone);
+    hipLaunchKernelGGL((gmx_indirect_session_kernel<false, true>), dim3(1), dim3(64), lds_bytes, stream, dv, banks,
+                       stream_idx, mc, mr, idle_ticks, replay_forward, (const GmxMatchDev*)nullptr, mnone, *cargs);
+  }
   return hipGetLastError();
 }
 

@@ -54,9 +54,19 @@ struct gmx_indirect {
   int match_k = 0, match_n_cols = 0;
   int32_t match_slot[GMX_MATCH_MAX_MODELS] = {};
   int32_t match_cols[GMX_MATCH_MAX_CTX_COLS] = {};
+  // gmx_indirect_attach_ctx: the streams of this context bank step at the head of a chained forward in the same
+  // waves.  As for the Match bank, what a wave needs is copied here at the attach (gmx_ctx.inc comes later), the two
+  // objects register with each other, and whichever is destroyed first detaches (ctx_host_detach).
+  gmx_ctx* ctx = nullptr;
+  const GmxCtxDev* ctx_dev_d = nullptr;
+  uint8_t* ctx_banks = nullptr;
+  uint64_t ctx_bank_bytes = 0;
+  const int32_t* ctx_routes_d = nullptr;  // [GMX_CTX_WAVE_ROUTE_WORDS]
+  int ctx_v = 0, ctx_n_mixer_cols = 0;
 };
 static void ind_ckpt_free(gmx_indirect* ib);
 static int match_host_detach(gmx_match* mb);  // gmx_match.inc
+static int ctx_host_detach(gmx_ctx* cb);      // gmx_ctx.inc
 static_assert(sizeof(((GmxIndMbCmd*)nullptr)->match_ctx[0]) == GMX_MATCH_MAX_MODELS * 4 &&
                   sizeof(((GmxIndMbReply*)nullptr)->match_pred) == GMX_MATCH_MAX_MODELS * 4,
               "the Match fields of the Indirect mailbox hold one lane group");
@@ -70,6 +80,12 @@ struct GmxIndMatchCmd {
   uint8_t* active;         // [K_match], nullable
   uint32_t* longest_match; // nullable
 };
+// What the context variables do at the head of a chained forward, and what they answer.
+struct GmxIndCtxCmd {
+  uint32_t what;           // the command's ctx_what word (gmx_ctx.h)
+  uint32_t* values;        // [V], nullable
+  uint32_t* bit_context;   // nullable
+};
 
 // ---- per-bit sessions: gmx_indirect_forward / gmx_indirect_learn without a kernel launch per call -----
 // The protocol and its bounded waits are gmx_mailbox.h, the blocks and the stream of a session GmxSessionHw
@@ -81,6 +97,7 @@ struct GmxIndSession : GmxSessionHw {
   uint32_t slot = 0, live_slot = 0;  // payload slot of the newest forward published / completed
   int pending_learn = 0;       // 1 + bit: noted by gmx_indirect_learn, not yet published
   bool fwd_live = false, learn_inflight = false;
+  uint32_t ctx_what[2] = {0, 0};  // host copy of the command block's ctx_what words (the block may be device memory)
 };
 static int ind_sessions_close(gmx_indirect* ib);
 static void ind_sessions_free(gmx_indirect* ib);
@@ -114,6 +131,10 @@ hipError_t gmx_launch_indirect_session_match(const GmxIndDev* dv, int k_ind, uin
                                              GmxIndMbCmd* mc, GmxIndMbReply* mr, unsigned long long idle_ticks,
                                              int replay_forward, const GmxMatchDev* mdv, const GmxMatchStepArgs* margs,
                                              unsigned lds_bytes, hipStream_t stream);
+hipError_t gmx_launch_indirect_session_ctx(const GmxIndDev* dv, int k_ind, uint8_t* banks, int stream_idx,
+                                           GmxIndMbCmd* mc, GmxIndMbReply* mr, unsigned long long idle_ticks,
+                                           int replay_forward, const GmxMatchDev* mdv, const GmxMatchStepArgs* margs,
+                                           const GmxCtxWaveArgs* cargs, unsigned lds_bytes, hipStream_t stream);
 }
 
 static void ind_batch_free(gmx_ind_batch* b) {
@@ -139,6 +160,7 @@ static void ind_batch_free(gmx_ind_batch* b) {
 extern "C" void gmx_indirect_destroy(gmx_indirect* ib) {
   if (!ib) return;
   (void)hipSetDevice(ib->device);
+  if (ib->ctx) (void)ctx_host_detach(ib->ctx);        // (stops the sessions; a noted learn takes the launch path)
   if (ib->match) (void)match_host_detach(ib->match);  // (stops the sessions; a noted Match learn takes the launch path)
   ind_sessions_free(ib);
   if (ib->stream) (void)hipStreamSynchronize(ib->stream);
@@ -545,14 +567,28 @@ static int ind_session_start(gmx_indirect* ib, int s) {
   if (rc) return rc;
   ind_session_note_done(se);
   const int replay = se->fwd_live ? 1 + (int)se->live_slot : 0;
+  GmxMatchStepArgs ma;
+  memset(&ma, 0, sizeof ma);
   if (ib->match) {  // the stream's Match models in lanes 56..63: the wave steps them as "stream 0" of these arguments
-    GmxMatchStepArgs ma;
-    memset(&ma, 0, sizeof ma);
     ma.banks = ib->match_banks + (uint64_t)s * ib->match_bank_bytes;
     ma.hist = ib->match_hist + (uint64_t)s * ib->match_hist_cap;
     ma.n_ctx_cols = ib->match_n_cols;
     for (int c = 0; c < ib->match_n_cols; ++c) ma.ctx_cols[c] = ib->match_cols[c];
     ma.n_streams = 1;
+  }
+  if (ib->ctx) {  // the stream's context variables at the head of a chained forward (a fresh wave reads the board itself)
+    GmxCtxWaveArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.dev = ib->ctx_dev_d;
+    ca.bank = ib->ctx_banks + (uint64_t)s * ib->ctx_bank_bytes;
+    ca.routes = ib->ctx_routes_d;
+    ca.n_mixer_cols = ib->ctx_n_mixer_cols;
+    HIPCHK(gmx_launch_indirect_session_ctx(ib->dev_d, ib->dev.k, ib->banks, s, se->mc, se->mb, kIdleTicks, replay,
+                                           ib->match ? ib->match_dev_d : nullptr, ib->match ? &ma : nullptr, &ca,
+                                           ib->lds_bytes + 4u * GMX_CTX_MAX_VARS, se->stream));
+    return GMX_OK;
+  }
+  if (ib->match) {
     HIPCHK(gmx_launch_indirect_session_match(ib->dev_d, ib->dev.k, ib->banks, s, se->mc, se->mb, kIdleTicks, replay,
                                              ib->match_dev_d, &ma, ib->lds_bytes, se->stream));
     return GMX_OK;
@@ -624,6 +660,33 @@ static int ind_session_stop(gmx_indirect* ib, int s) {
   return session_hw_stop(se, [&] { return ind_session_wait(ib, s); });
 }
 
+// The board of the context bank that rides here is about to be moved for stream s by something that is not a command
+// of the stream's wave (a launch of the per-bit surface, a run, a board written, a copy, a reset).  A forward that took
+// its table indices from the board and still waits for its learn would be recomputed from the MOVED board by a wave
+// restarted in between (gmx_ctx_step_wave_replay), and its learn would land on other entries.  So a noted learn is run
+// now -- the wave, restarted if it has left, replays from the board as it still stands -- and without one the forward
+// is void from here on, as after a change of the Indirect bank's own content (ind_sessions_drop_forward): it is what a
+// perceived bit leaves behind (generation: no learn ever comes), and a gmx_indirect_learn that does come for it
+// returns GMX_ERR_STATE with no table touched.  s < 0: every stream.
+static int ind_ctx_board_moves(gmx_indirect* ib, int s) {
+  for (int i = 0; i < (int)ib->sessions.size(); ++i) {
+    GmxIndSession* se = ib->sessions[i];
+    if (!se || se->dead || (s >= 0 && i != s)) continue;
+    ind_session_note_done(se);
+    if (!se->fwd_live || !(se->ctx_what[se->live_slot] & GMX_STEP_PREDICT)) continue;
+    if (se->pending_learn) {
+      int rc = ind_session_flush_learn(ib, i);
+      if (rc) return rc;
+    }
+    if (se->learn_inflight) {
+      int rc = ind_session_wait(ib, i);
+      if (rc) return rc;
+    }
+    se->fwd_live = false;  // (no learn was noted for it)
+  }
+  return GMX_OK;
+}
+
 static void ind_sessions_drop_forward(gmx_indirect* ib, int stream) {
   for (size_t s = 0; s < ib->sessions.size(); ++s) {
     GmxIndSession* se = ib->sessions[s];
@@ -648,7 +711,7 @@ static void ind_sessions_free(gmx_indirect* ib) {
 static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts, uint32_t bit_context,
                                float* predictions, uint8_t* active, uint32_t chain_word = 0,
                                uint32_t chain_slot = 0, void* chain_mc = nullptr,
-                               const GmxIndMatchCmd* match = nullptr) {
+                               const GmxIndMatchCmd* match = nullptr, const GmxIndCtxCmd* ctx = nullptr) {
   {
     // a noted learn rides along only if the wave that made its forward is still there
     GmxIndSession* se0 = s < (int)ib->sessions.size() ? ib->sessions[s] : nullptr;
@@ -665,7 +728,7 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
   const int K = ib->dev.k;
   uint32_t img[GMX_IND_MAX_MODELS];
   memset(img, 0, sizeof img);
-  memcpy(img, contexts, (size_t)K * 4);
+  if (contexts) memcpy(img, contexts, (size_t)K * 4);  // (null: every column is the context bank's)
   // the other payload slot: the one of the forward still waiting for its learn stays intact (a wave
   // restarted in between recomputes that forward from it)
   se->slot ^= 1u;
@@ -674,11 +737,15 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
   if (ib->match) {  // (every forward says what the Match lanes do: nothing, unless this is their chained forward)
     if (match) {
       uint32_t mimg[GMX_MATCH_MAX_MODELS] = {0};
-      memcpy(mimg, match->ctx, (size_t)ib->match_k * 4);
+      if (match->ctx) memcpy(mimg, match->ctx, (size_t)ib->match_k * 4);
       memcpy(se->mc->match_ctx[se->slot], mimg, sizeof mimg);
     }
     se->mc->match_what[se->slot] = (match && chain_word) ? match->what : 0u;
   }
+  // (likewise, and whatever is attached: a slot never keeps the word of an earlier forward, which a wave with the
+  // context phase, started after a later attach, would take for this forward's in a replay)
+  se->ctx_what[se->slot] = (ib->ctx && ctx && chain_word) ? ctx->what : 0u;
+  se->mc->ctx_what[se->slot] = se->ctx_what[se->slot];
   se->mc->chain_slot = chain_slot;
   se->mc->chain_mc = (uint64_t)(uintptr_t)chain_mc;
   se->mc->chain_word = chain_word;
@@ -706,6 +773,10 @@ static int ind_session_forward(gmx_indirect* ib, int s, const uint32_t* contexts
       if (match->active) match->active[i] = (uint8_t)(se->mb->match_active[i] != 0u);
     }
     if (match->longest_match) *match->longest_match = se->mb->longest_match;
+  }
+  if (ib->ctx && ctx && chain_word) {
+    if (ctx->bit_context) *ctx->bit_context = se->mb->ctx_bit_context;
+    if (ctx->values && (ctx->what & GMX_CTX_WAVE_VALUES)) memcpy(ctx->values, se->mb->ctx_values, (size_t)ib->ctx_v * 4);
   }
   return GMX_OK;
 }

@@ -238,8 +238,14 @@ struct GmxIndMbCmd {       // host -> device: fine-grained device memory behind 
   // forward, and in a replayed one).
   uint32_t match_ctx[2][8];  // [GMX_MATCH_MAX_MODELS]
   uint32_t match_what[2];
-  uint32_t pad2[6];
+  // The stream's context variables stepping in the same wave (gmx_indirect_attach_ctx), per payload slot: what they do
+  // at the head of a chained forward -- GMX_CTX_STEP_LEARN | _PREDICT, GMX_CTX_WAVE_VALUES | _RELOAD, and in bit 8 the
+  // coded bit of that Learn (gmx_ctx.h).  0: the command's contexts and bit_context are the host's.  The routed
+  // columns of ctx / match_ctx and bit_context of such a command are not read.
+  uint32_t ctx_what[2];
+  uint32_t pad2[4];
 };
+static_assert(sizeof(GmxIndMbCmd) == 672, "ctx_what came out of pad2: the command block keeps its size");
 #define GMX_IND_MB_MATCH_BIT_SHIFT 8
 struct GmxIndMbReply {     // device -> host: pinned host memory
   uint32_t done_seq;
@@ -252,7 +258,10 @@ struct GmxIndMbReply {     // device -> host: pinned host memory
   float match_pred[8];                 // [GMX_MATCH_MAX_MODELS]
   uint32_t match_active[8];
   uint32_t longest_match;
-  uint32_t pad2[15];
+  // the context variables of a chained forward that carried them: bit_context, and the V values when asked for
+  uint32_t ctx_bit_context;
+  uint32_t pad2[14];
+  uint32_t ctx_values[64];             // [GMX_CTX_MAX_VARS]
 };
 
 struct GmxIndRunArgs {

@@ -642,6 +642,7 @@ extern "C" int gmx_indirect_attach_match(gmx_indirect* ib, gmx_match* mb, const 
       if (mb->dev.m[i].slot == ib->dev.m[j].slot_a || mb->dev.m[i].slot == ib->dev.m[j].slot_b) return GMX_ERR_INVALID;
   if (!mb->chainsteps.empty()) return GMX_ERR_STATE;            // one host of its per-bit state at a time
   if (mb->host && mb->host != ib) return GMX_ERR_STATE;
+  if (ib->ctx) return GMX_ERR_STATE;  // (gmx_indirect_attach_ctx's routes were made for the banks there were: Match first)
   HIPCHK(hipSetDevice(ib->device));
   int rc = ib->match ? match_host_detach(ib->match) : GMX_OK;  // (another bank, or this one with other columns)
   if (rc) return rc;

@@ -148,6 +148,17 @@ class CtxGroup:
         check(self.L.gmx_ctx_run_ragged(self.h, batch.h, nb.ctypes.data_as(C.POINTER(C.c_uint64)),
                                         C.byref(targets) if targets is not None else None), "gmx_ctx_run_ragged")
 
+    def forward(self, stream=0):
+        """gmx_ctx_forward: one record of run() for one stream.  Returns (values [V], bit_context)."""
+        vals = np.zeros(self.V, np.uint32)
+        bc = C.c_uint32(0)
+        check(self.L.gmx_ctx_forward(self.h, stream, _vp(vals), C.byref(bc)), "gmx_ctx_forward")
+        return vals, bc.value
+
+    def learn(self, bit, stream=0):
+        """gmx_ctx_learn: `bit` becomes the blackboard's new_bit (a learned or a perceived bit alike)."""
+        check(self.L.gmx_ctx_learn(self.h, stream, int(bit)), "gmx_ctx_learn")
+
     def blackboard(self, stream=0):
         bb = CtxBlackboard()
         check(self.L.gmx_ctx_blackboard_get(self.h, stream, C.byref(bb)), "gmx_ctx_blackboard_get")

@@ -35,6 +35,7 @@ class IndirectGroup:
               "gmx_indirect_create")
         self.h = h
         self.match = None
+        self.ctx = None
 
     def set_cu_mask(self, words=None):
         """Compute units this bank's kernels may use: 32-bit words, bit i = CU i (None: all)."""
@@ -124,6 +125,56 @@ class IndirectGroup:
                                              _vp(ac), len(ac), _vp(mc), C.byref(p), _vp(out), _vp(pred), _vp(act),
                                              _vp(mpred), _vp(mact), C.byref(lm)), "gmx_chain_forward_match")
         return p.value, out, pred, act, mpred, mact, lm.value
+
+    def attach_ctx(self, cg, mixer_route=None, ind_route=None, match_route=None):
+        """gmx_indirect_attach_ctx: the streams of the CtxGroup `cg` step at the head of a chained forward in this
+        bank's per-bit session waves.  A route has a variable index per column, -1 for a column that stays the
+        caller's.  cg=None detaches."""
+        if cg is None:
+            check(self.L.gmx_indirect_attach_ctx(self.h, None, None), "gmx_indirect_attach_ctx")
+            self.ctx = None
+            return
+        r = _lib.CtxStepRoutes()
+        keep = []
+        for name, route in (("mixer", mixer_route), ("ind", ind_route), ("match", match_route)):
+            if route is None:
+                continue
+            a = np.ascontiguousarray(route, np.int32)
+            keep.append(a)
+            setattr(r, name + "_route", a.ctypes.data_as(C.POINTER(C.c_int32)))
+            setattr(r, "n_" + name + "_route", len(a))
+        check(self.L.gmx_indirect_attach_ctx(self.h, cg.h, C.byref(r)), "gmx_indirect_attach_ctx")
+        # (the C objects register with each other, so either may be closed first; the reference keeps the Python
+        # object, whose __del__ destroys the bank, alive for as long as this one may use it)
+        self.ctx = cg
+
+    def chain_forward_ctx(self, group, predictions, active, mixer_contexts, contexts=None, match_contexts=None,
+                          stream=0):
+        """gmx_chain_forward_ctx: the attached context bank's Predict, the attached Match bank's (if any), this bank's
+        and the mixers' as one call; the routed columns and bit_context are the context bank's.  Returns a dict: p,
+        out, pred, act, (mpred, mact, lm with a Match bank), values [V], bit_context."""
+        cg, mg = getattr(self, "ctx", None), self.match
+        assert cg is not None
+        c = np.ascontiguousarray(contexts, np.uint32) if contexts is not None else None
+        mx = np.ascontiguousarray(match_contexts, np.uint32) if match_contexts is not None else None
+        pr = np.ascontiguousarray(predictions, np.float32)
+        ac = np.ascontiguousarray(active, np.int32)
+        mc = np.ascontiguousarray(mixer_contexts, np.uint32)
+        assert pr.shape == (group.topo.n_inputs,) and mc.shape == (group.topo.n_mixers,)
+        assert c is None or c.shape == (self.K,)
+        assert mx is None or (mg is not None and mx.shape == (mg.K,))
+        p = C.c_float()
+        km = mg.K if mg is not None else 1
+        r = dict(out=np.zeros(group.topo.n_mixers, np.float32), pred=np.zeros(2 * self.K, np.float32),
+                 act=np.zeros(2 * self.K, np.uint8), mpred=np.zeros(km, np.float32), mact=np.zeros(km, np.uint8),
+                 values=np.zeros(cg.V, np.uint32))
+        lm, bc = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.gmx_chain_forward_ctx(self.h, group.h, stream, _vp(c), _vp(mx), _vp(pr), _vp(ac), len(ac), _vp(mc),
+                                           C.byref(p), _vp(r["out"]), _vp(r["pred"]), _vp(r["act"]), _vp(r["mpred"]),
+                                           _vp(r["mact"]), C.byref(lm), _vp(r["values"]), C.byref(bc)),
+              "gmx_chain_forward_ctx")
+        r.update(p=p.value, lm=lm.value, bit_context=bc.value)
+        return r
 
     def run(self, batch, n_bits=None, learn=True, into=None, timed=False):
         n_bits = batch.max_bits if n_bits is None else n_bits

@@ -689,8 +689,9 @@ int gmx_lstm_set_cu_mask(gmx_lstm* l, const uint32_t* mask, int n_words);
  * (recent_bits, last_byte, rotating_history, recent_bytes), for S streams on one device.  A bank is described by an
  * ordered list of V <= 64 variables; a run writes, for every bit, the values the variables have at Predict of that
  * bit -- into a debugging array of the bank's own batch and into the context columns of up to three record batches
- * of the other banks.  In the lock-step chain the bank steps a bit at a time (gmx_chainstep_attach_ctx below).  The
- * adapter (dropin/) and the per-bit sessions do not use these banks yet. */
+ * of the other banks.  In the lock-step chain the bank steps a bit at a time (gmx_chainstep_attach_ctx below), and so it
+ * does on the per-bit surface (gmx_ctx_forward / gmx_ctx_learn) and in the per-bit session chain
+ * (gmx_indirect_attach_ctx / gmx_chain_forward_ctx).  The adapter (dropin/) does not use these banks yet. */
 typedef enum gmx_ctx_kind {
   GMX_CTX_ZERO = 0,             /* always_zero */
   GMX_CTX_BIT_CONTEXT = 1,      /* bit_context = recent_bits - 1 */
@@ -883,6 +884,55 @@ uint64_t gmx_chainstep_commit_bytes(const gmx_chainstep* cs);
 /* gmx_chainstep_step with HIP events recorded around the step's graph on the group's stream: *device_ms is what the
  * device spent on the step (0 when no stream asked for anything).  For scripts/bench_chainstep_ctx.py. */
 int gmx_chainstep_timed_step(gmx_chainstep* cs, float* device_ms);
+
+/* ==== The context variables one bit at a time ========================================================
+ * gmx_ctx_forward is exactly one record of gmx_ctx_run for one stream: values ([V], nullable) receives every variable
+ * at Predict of that bit, bit_context (nullable) ShortTermMemory::bit_context.  One launch and one wait.
+ * gmx_ctx_learn makes `bit` the blackboard's new_bit -- what Predictor::Learn and Predictor::Perceive both leave for the
+ * next BasicContexts::Predict, so a generated bit is perceived through the same call.  It is only noted and travels
+ * with the stream's next forward; any other gmx_ctx_* call that reads or writes the stream runs a noted learn first.
+ * A second forward of a stream without a learn in between returns GMX_ERR_STATE, and between a forward and its learn
+ * the rules gmx_chainstep_attach_ctx gives for gmx_ctx_run / _run_ragged, _blackboard_get, _copy, _blackboard_set and
+ * _reset hold unchanged.  A bank attached to a gmx_chainstep refuses both calls with GMX_ERR_STATE.  A stream may move
+ * between this surface, gmx_ctx_run and the session chain below anywhere inside a byte. */
+int gmx_ctx_learn(gmx_ctx* cb, int stream, int bit);
+int gmx_ctx_forward(gmx_ctx* cb, int stream, uint32_t* values /* [V], nullable */, uint32_t* bit_context /* nullable */);
+
+/* ==== The context variables in the per-bit session chain: the host sends one bit =======================
+ * gmx_indirect_attach_ctx: the streams of `cb` (same stream count and device as ib) step in ib's per-bit session waves,
+ * as a phase at the head of a chained forward.  routes has the meaning it has for gmx_chainstep_attach_ctx: mixer_route
+ * is required, its length is checked against the group's M by the forward (GMX_ERR_INVALID there); ind_route is
+ * required; match_route is given iff a Match bank is attached to ib already (attach the Match bank first:
+ * gmx_indirect_attach_match on a bank with a context bank attached returns GMX_ERR_STATE); a routed mixer column must not
+ * be one of the Match bank's ctx_columns.  cb == NULL detaches.  GMX_ERR_STATE: cb is attached to a gmx_chainstep or to
+ * another Indirect bank; gmx_chainstep_attach_ctx on a bank that rides here returns it too.  The two objects register
+ * with each other; destroying either detaches first.
+ *
+ * gmx_chain_forward_ctx: gmx_ctx_forward, then gmx_chain_forward_match (gmx_chain_forward when no Match bank is
+ * attached to ib) with the routed columns of ind_contexts, match_contexts and contexts, and bit_context, taken from
+ * the bank: the same floats and the same state in every bank as those calls one after the other.  ind_contexts /
+ * match_contexts are read only in columns routed -1 and may be NULL when there is none; routed columns of `contexts`
+ * are ignored.  ctx_values ([V]) and bit_context are outputs, nullable.  The learns are the usual calls
+ * (gmx_ctx_learn, gmx_match_learn, gmx_indirect_learn, gmx_bank_learn): all are noted and travel with the next
+ * forward.  Under gmx_chain_forward's own conditions for its one-round-trip path (same device, both banks on sessions,
+ * stock-shape mixers, n_active >= 0, K <= 56 with a Match bank) the call is ONE command and ONE wait, and no context
+ * word crosses the link; otherwise, or when no session slot is free, it is the launches one after the other.
+ * Everything is validated before any bank moves.  GMX_ERR_STATE: nothing attached; a second forward of the stream
+ * without gmx_ctx_learn (or, with a Match bank, without gmx_match_learn).  Every other gmx_ctx_* call that reads or
+ * writes an attached bank (gmx_ctx_forward, the runs, the blackboards, copy, reset, export / import, the group calls)
+ * first stops ib's sessions and runs a noted learn.  A wave restarted between a chained forward and its Indirect learn
+ * recomputes the models' table indices from the blackboard's values, so whatever would move a stream's blackboard
+ * outside its wave -- gmx_ctx_forward, the launch route of gmx_chain_forward_ctx, gmx_ctx_run / _run_ragged with bits
+ * for the stream, gmx_ctx_blackboard_set, gmx_ctx_group_blackboard_set, gmx_ctx_copy into it, gmx_ctx_reset -- first
+ * runs the Indirect learn noted for that forward.  When gmx_indirect_learn has not been called for it by then the
+ * forward is void (a perceived bit's never is learned): a gmx_indirect_learn that comes afterwards returns
+ * GMX_ERR_STATE and touches no table. */
+int gmx_indirect_attach_ctx(gmx_indirect* ib, gmx_ctx* cb, const gmx_ctx_step_routes* routes);
+int gmx_chain_forward_ctx(gmx_indirect* ib, gmx_group* g, int stream, const uint32_t* ind_contexts,
+                          const uint32_t* match_contexts, const float* predictions, const int32_t* active_models,
+                          int n_active, const uint32_t* contexts, float* p_final, float* out_all,
+                          float* ind_predictions, uint8_t* ind_active, float* match_predictions,
+                          uint8_t* match_active, uint32_t* longest_match, uint32_t* ctx_values, uint32_t* bit_context);
 
 #ifdef __cplusplus
 }
