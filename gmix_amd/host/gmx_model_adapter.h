@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "model.h"  // the reference's (src/model.h): Model, ShortTermMemory, LongTermMemory
+#include "contexts/basic-contexts.h"  // ... and its BasicContexts, which gmx::GpuBasicContexts forwards to
 
 #include "gmxmix.h"  // include/gmxmix.h
 
@@ -66,6 +67,15 @@ class GpuIndirectBank;
 class GpuLstmModel;
 class GpuMatch;
 class GpuMatchBank;
+class GpuCtxBank;
+
+// Where the context bank writes in the other banks' records (gmx_ctx_targets / gmx_ctx_step_routes): one entry per
+// context column, the variable it receives or -1.
+struct CtxRoutes {
+  std::vector<int32_t> mixers, indirect, match;
+  bool operator==(const CtxRoutes& o) const { return mixers == o.mixers && indirect == o.indirect && match == o.match; }
+  bool operator!=(const CtxRoutes& o) const { return !(*this == o); }
+};
 
 // Process-wide tables of the adapters.  The reference lets several Predictors live in one process
 // (runner-utils.cpp:291-292); here they may also be built and run on different threads (one file per thread,
@@ -88,7 +98,8 @@ inline bool ChainFused() {
 // the host-side feature models of a Predictor can run T bits ahead while the device works on the T bits before:
 // the device-side models' Predict then only RECORDS its inputs and Learn the coded bit, straight into the pinned
 // arrays of the banks' batches -- the mixers {predictions, active_models, 33 contexts, bit}, the Indirect models
-// {41 contexts, bit_context, bit}, the LSTM {PPM byte distribution, byte} -- a full chunk is uploaded and run
+// {41 contexts, bit_context, bit}, the LSTM {PPM byte distribution, byte}, the Match models {6 contexts, bit_context, bit},
+// the context bank {bit} (which then fills the others' context columns on the device) -- a full chunk is uploaded and run
 // behind the chunk before it (a ring of four sets of batches, MixerPool::kRing) and its
 // probabilities come back one chunk later, in order, to whoever consumes them (the arithmetic coder:
 // gmx_batched.h).
@@ -115,6 +126,10 @@ struct RunAheadView {
   const uint8_t* match_active = nullptr;   // [n][n_match] whether SetPrediction marked them active
   const uint32_t* match_longest = nullptr; // [n] ShortTermMemory::longest_match after the Match models' Predict
   int n_match = 0;
+  // with the context objects on the device (gmx::GpuCtxBank), and only when the ring was made for a sink that asked for
+  // the models (RunAheadSink::WantsModels):
+  const uint32_t* ctx_values = nullptr;    // [n][n_ctx_vars] every context variable at Predict of every bit
+  int n_ctx_vars = 0;
 };
 struct RunAheadSink {
   virtual ~RunAheadSink() {}
@@ -152,8 +167,10 @@ class MixerPool {
       if (iring_[k]) gmx_ind_batch_destroy(iring_[k]);
       if (lring_[k]) gmx_lstm_batch_destroy(lring_[k]);
       if (mring_[k]) gmx_match_batch_destroy(mring_[k]);
+      if (cring_[k]) gmx_ctx_batch_destroy(cring_[k]);
     }
     if (cs_) gmx_chainstep_destroy(cs_);
+    if (ctx_) gmx_ctx_destroy(ctx_);
     if (match_) gmx_match_destroy(match_);
     if (group_) gmx_group_destroy(group_);
     if (ind_) gmx_indirect_destroy(ind_);
@@ -237,6 +254,7 @@ class MixerPool {
   gmx_indirect* indirect() const { return ind_; }
   gmx_lstm* lstm() const { return lstm_; }
   gmx_match* match() const { return match_; }
+  gmx_ctx* ctx() const { return ctx_; }
   // Bytes of input history every stream's Match models can hold (gmx_match_create wants it up front): to be called
   // before the first Predictor of the pool is used.  Without it: $GMX_MATCH_HISTORY, else kDefaultMatchHistory.  A run
   // that would take a history past it ends with GMX_ERR_INVALID before anything is queued.
@@ -260,7 +278,7 @@ class MixerPool {
   double submit_seconds() const { return submit_seconds_; }
   double wait_seconds() const { return wait_seconds_; }
 
-  enum Parts { kMixers = 1, kIndirect = 2, kLstm = 4, kMatch = 8 };
+  enum Parts { kMixers = 1, kIndirect = 2, kLstm = 4, kMatch = 8, kCtx = 16 };
 
   // ---- lock step (decoding).  A decoder learns each bit from Predict's own result (coder/decoder.cpp:19-39), so
   // the Predictors of a pool that decode advance together, one device step (gmx_chainstep) per coded bit: every
@@ -311,6 +329,7 @@ class MixerPool {
   friend class GpuIndirectBank;
   friend class GpuLstmModel;
   friend class GpuMatchBank;
+  friend class GpuCtxBank;
 
   struct Stream {  // one Predictor's place in the pool
     const LongTermMemory* owner = nullptr;
@@ -319,6 +338,7 @@ class MixerPool {
     GpuIndirectBank* indirect = nullptr;
     GpuLstmModel* lstm = nullptr;
     GpuMatchBank* match = nullptr;
+    GpuCtxBank* cbank = nullptr;
     // run-ahead: where the chunk being filled is recorded, and how many bits of it are
     bool ra = false;
     uint64_t t = 0;
@@ -331,6 +351,10 @@ class MixerPool {
     uint8_t* bytes = nullptr;
     uint32_t *mctx = nullptr, *mbc = nullptr;
     uint8_t* mbits = nullptr;
+    uint8_t* cbits = nullptr;  // the context bank's only record: the coded bit
+    // run-ahead and lock step with a context bank: the columns it writes on the device (the adapters leave them, and the
+    // Indirect and Match records' bit_contexts and bits, alone); null without one
+    const CtxRoutes* croutes = nullptr;
     uint8_t m_last_active[8] = {};  // the Match models' active flags of the newest bit that came back ...
     bool m_last_valid = false;      // ... if one did (the sink asked for models)
     bool ls = false;  // lock step: Predict records into the chainstep's arrays and waits for the step
@@ -460,6 +484,16 @@ class MixerPool {
     mdescs_ = d;
     return gmx_match_create(&match_, d.data(), (int)d.size(), match_cap_, S_, device_);
   }
+  int EnsureCtx(const std::vector<gmx_ctx_desc>& d) {  // (the descriptors are zero-filled before they are set)
+    if (ctx_) {
+      bool same = d.size() == cdescs_.size();
+      for (size_t i = 0; same && i < d.size(); ++i) same = memcmp(&d[i], &cdescs_[i], sizeof(gmx_ctx_desc)) == 0;
+      return same ? GMX_OK : GMX_ERR_INVALID;
+    }
+    cdescs_ = d;
+    ctx_used_.assign(S_, 0);
+    return gmx_ctx_create(&ctx_, d.data(), (int)d.size(), S_, device_);
+  }
 
   // ---- the ring ----
   // parts: which banks of the stream's Predictor are on the device (all streams of a pool alike);
@@ -467,10 +501,12 @@ class MixerPool {
   // (gmx_lstm_feed); models: the sink wants the feature models' predictions back as well
   // match_cols: the gate-context columns that read ShortTermMemory::longest_match (gmx_match_run's ctx_columns)
   int Join(int slot, uint64_t chunk_bits, int parts, int lstm_slot, int mixer_ctx_col, int ind_ctx_col, bool models,
-           bool all_outputs, const std::vector<int32_t>& match_cols = std::vector<int32_t>()) {
+           bool all_outputs, const std::vector<int32_t>& match_cols = std::vector<int32_t>(),
+           const CtxRoutes& ctx_routes = CtxRoutes()) {
     std::unique_lock<std::mutex> lk(mu_);
     if (status_.load()) return status_.load();
     if (!ring_[0]) {
+      ctx_routes_ = ctx_routes;
       T_ = chunk_bits < 8 ? 8 : chunk_bits & ~7ull;
       parts_ = parts;
       lstm_slot_ = lstm_slot;
@@ -508,6 +544,16 @@ class MixerPool {
           if (!gmx_match_batch_contexts(mring_[k]) || !gmx_match_batch_bit_contexts(mring_[k]) || !gmx_match_batch_bits(mring_[k]))
             return Fail("gmx_match_batch (pinned arrays)", GMX_ERR_NOMEM);
         }
+        if (parts_ & kCtx) {
+          // the coded bits and nothing else; the values come back only for a sink that analyses (208 bytes per bit for
+          // the stock variables), and only when the ring's first stream asked
+          ctx_values_ = models;
+          V_ = gmx_ctx_n_vars(ctx_);
+          if ((rc = gmx_ctx_batch_create(&cring_[k], ctx_, T_, ctx_values_ ? GMX_CTX_BATCH_VALUES : 0)))
+            return Fail("gmx_ctx_batch_create", rc);
+          if (!gmx_ctx_batch_bits(cring_[k]) || (ctx_values_ && !gmx_ctx_batch_values(cring_[k])))
+            return Fail("gmx_ctx_batch (pinned arrays)", GMX_ERR_NOMEM);
+        }
       }
       n_pad_ = gmx_batch_n_pad(ring_[0]);
       mask_words_ = gmx_batch_mask_words(ring_[0]);
@@ -518,13 +564,15 @@ class MixerPool {
       for (int k = 0; k < kRing; ++k) n_in_[k].assign(S_, 0);
       n_bytes_.assign(S_, 0);
     } else if (parts != parts_ || lstm_slot != lstm_slot_ || mixer_ctx_col != mixer_ctx_col_ || ind_ctx_col != ind_ctx_col_ ||
-               match_cols != match_cols_ || (all_outputs && !all_outputs_)) {
+               match_cols != match_cols_ || ctx_routes != ctx_routes_ || (all_outputs && !all_outputs_) ||
+               ((parts_ & kCtx) && models && !ctx_values_)) {  // (a ring made without the context bank's values array)
       return GMX_ERR_INVALID;  // Predictors of different make in one pool (or a sink that needs what the ring does not carry)
     }
     models_back_ = models_back_ || models;
     n_cur_[slot] = 0;
     for (int k = 0; k < kRing; ++k) n_in_[k][slot] = 0;
     streams_[slot].ra = true;
+    streams_[slot].croutes = (parts_ & kCtx) ? &ctx_routes_ : nullptr;
     streams_[slot].t = 0;
     streams_[slot].m_last_valid = false;
     Records(slot);
@@ -553,6 +601,7 @@ class MixerPool {
       st.mbc = gmx_match_batch_bit_contexts(mring_[cur_]) + (size_t)slot * T_;
       st.mbits = gmx_match_batch_bits(mring_[cur_]) + (size_t)slot * T_;
     }
+    if (parts_ & kCtx) st.cbits = gmx_ctx_batch_bits(cring_[cur_]) + (size_t)slot * T_;
   }
   // Every stream has handed in its chunk: queue it behind the chunk before, wait for THAT one.  mu_ held.
   void Lead() {
@@ -595,6 +644,7 @@ class MixerPool {
       }
       // (the Match bank's transfers run on its own stream, behind the kernel that wrote the results)
       if (models_back_ && (parts_ & kMatch)) GMX_POOL_STEP(gmx_match_batch_download(mring_[other], on));
+      if (ctx_values_ && (parts_ & kCtx)) GMX_POOL_STEP(gmx_ctx_batch_download(cring_[other], on));  // (likewise)
     }
     const auto lead_tw = std::chrono::steady_clock::now();
     if (maxn > 0) {
@@ -612,6 +662,31 @@ class MixerPool {
         // for the upload above and for the writer before it, so any place between the upload and the mixers' run is
         // right; this one is first because it waits for nothing else (gmx_lstm_feed stands behind the LSTM's kernels).
         GMX_POOL_STEP(gmx_match_batch_upload(mring_[c], maxn));
+      }
+      if (parts_ & kCtx) {
+        // BasicContexts' fields, IntervalContext x 9, SkipContext x 20, IndirectHash x 9 of every bit of the chunk, from
+        // the coded bits alone: the routed context columns of the three record batches (and the Indirect and Match
+        // batches' bit_contexts and bits) are written on the device, behind the batches' own uploads above and in front
+        // of every kernel that reads them.
+        gmx_ctx_targets tg;
+        memset(&tg, 0, sizeof tg);
+        tg.mixers = ring_[c];
+        tg.mixer_route = ctx_routes_.mixers.data();
+        tg.n_mixer_route = (int32_t)ctx_routes_.mixers.size();
+        if (parts_ & kIndirect) {
+          tg.indirect = iring_[c];
+          tg.ind_route = ctx_routes_.indirect.data();
+          tg.n_ind_route = (int32_t)ctx_routes_.indirect.size();
+        }
+        if (parts_ & kMatch) {
+          tg.match = mring_[c];
+          tg.match_route = ctx_routes_.match.data();
+          tg.n_match_route = (int32_t)ctx_routes_.match.size();
+        }
+        GMX_POOL_STEP(gmx_ctx_batch_upload(cring_[c], maxn));
+        GMX_POOL_STEP(gmx_ctx_run_ragged(ctx_, cring_[c], n_cur_.data(), &tg));
+      }
+      if (parts_ & kMatch) {
         GMX_POOL_STEP(gmx_match_run_ragged(match_, mring_[c], n_cur_.data(), ring_[c], match_cols_.data(), (int)match_cols_.size()));
       }
       if (parts_ & kLstm) {
@@ -639,6 +714,7 @@ class MixerPool {
       if (models_back_ && (parts_ & kIndirect)) GMX_POOL_STEP(gmx_ind_batch_wait(iring_[other]));
       if (parts_ & kLstm) GMX_POOL_STEP(gmx_lstm_batch_wait(lring_[other]));
       if (models_back_ && (parts_ & kMatch)) GMX_POOL_STEP(gmx_match_batch_wait(mring_[other]));
+      if (ctx_values_ && (parts_ & kCtx)) GMX_POOL_STEP(gmx_ctx_batch_wait(cring_[other]));
     }
 #undef GMX_POOL_STEP
     if (rc) Fail(what, rc);
@@ -700,6 +776,10 @@ class MixerPool {
         streams_[slot].m_last_valid = true;
       }
     }
+    if (ctx_values_ && (parts_ & kCtx)) {
+      v->ctx_values = gmx_ctx_batch_values(cring_[cur_]) + (size_t)slot * T_ * V_;
+      v->n_ctx_vars = V_;
+    }
     n_in_[cur_][slot] = 0;
     streams_[slot].t = 0;
     Records(slot);
@@ -712,6 +792,7 @@ class MixerPool {
   void Leave(int slot) {
     std::unique_lock<std::mutex> lk(mu_);
     streams_[slot].ra = false;
+    streams_[slot].croutes = nullptr;
     if (participants_ > 0) --participants_;
     if (!n_cur_.empty()) n_cur_[slot] = 0;
     if (participants_ > 0 && arrived_ >= participants_ && status_.load() == 0) Lead();
@@ -719,7 +800,8 @@ class MixerPool {
 
   // ---- lock step ----
   int JoinLockstep(int slot, int parts, int lstm_slot, int mixer_ctx_col, int ind_ctx_col,
-                   const std::vector<int32_t>& match_cols = std::vector<int32_t>()) {
+                   const std::vector<int32_t>& match_cols = std::vector<int32_t>(),
+                   const CtxRoutes& ctx_routes = CtxRoutes()) {
     std::unique_lock<std::mutex> lk(mu_);
     if (status_.load()) return status_.load();
     if (ring_[0]) return GMX_ERR_STATE;  // (a pool runs ahead or steps, not both)
@@ -733,6 +815,23 @@ class MixerPool {
         if (!gmx_chainstep_match_contexts(cs_) || !gmx_chainstep_bit_contexts(cs_))
           return Fail("gmx_chainstep (match records)", GMX_ERR_NOMEM);
       }
+      if (parts & kCtx) {  // behind the Match bank's attach; the routed columns and bit_contexts are the device's from here on
+        gmx_ctx_step_routes r;
+        memset(&r, 0, sizeof r);
+        r.mixer_route = ctx_routes.mixers.data();
+        r.n_mixer_route = (int32_t)ctx_routes.mixers.size();
+        if (parts & kIndirect) {
+          r.ind_route = ctx_routes.indirect.data();
+          r.n_ind_route = (int32_t)ctx_routes.indirect.size();
+        }
+        if (parts & kMatch) {
+          r.match_route = ctx_routes.match.data();
+          r.n_match_route = (int32_t)ctx_routes.match.size();
+        }
+        rc = gmx_chainstep_attach_ctx(cs_, ctx_, &r);
+        if (rc) return Fail("gmx_chainstep_attach_ctx", rc);
+      }
+      ctx_routes_ = ctx_routes;
       match_cols_ = match_cols;
       parts_ = parts;
       lstm_slot_ = lstm_slot;
@@ -745,10 +844,11 @@ class MixerPool {
       mask_words_ = (n_inputs_ + 31) / 32;
       ls_what_ = gmx_chainstep_what(cs_);
     } else if (parts != parts_ || lstm_slot != lstm_slot_ || mixer_ctx_col != mixer_ctx_col_ || ind_ctx_col != ind_ctx_col_ ||
-               match_cols != match_cols_) {
+               match_cols != match_cols_ || ctx_routes != ctx_routes_) {
       return GMX_ERR_INVALID;
     }
     streams_[slot].ls = true;
+    streams_[slot].croutes = (parts_ & kCtx) ? &ctx_routes_ : nullptr;
     ++ls_participants_;
     return GMX_OK;
   }
@@ -756,6 +856,7 @@ class MixerPool {
     std::unique_lock<std::mutex> lk(mu_);
     if (streams_[slot].ls) {
       streams_[slot].ls = false;
+      streams_[slot].croutes = nullptr;
       if (ls_participants_ > 0) --ls_participants_;
     }
   }
@@ -788,6 +889,10 @@ class MixerPool {
   uint64_t match_cap_ = 0;  // 0: not set (EnsureMatch then takes the environment's or the default)
   std::vector<gmx_match_desc> mdescs_;
   std::vector<int32_t> match_cols_;
+  gmx_ctx* ctx_ = nullptr;
+  std::vector<gmx_ctx_desc> cdescs_;
+  std::vector<uint8_t> ctx_used_;  // [S] a Predictor has moved the stream's context bank (the next one starts it afresh)
+  CtxRoutes ctx_routes_;
   int n_inputs_ = 0;
   std::vector<gmx_mixer_desc> descs_;
   std::vector<int32_t> skip_;
@@ -809,16 +914,17 @@ class MixerPool {
   gmx_ind_batch* iring_[kRing] = {};
   gmx_lstm_batch* lring_[kRing] = {};
   gmx_match_batch* mring_[kRing] = {};
+  gmx_ctx_batch* cring_[kRing] = {};
   bool busy_[kRing] = {};
   uint64_t maxn_[kRing] = {};   // bits of the longest stream of the chunk in each ring slot
   int cur_ = 0, parts_ = 0, lstm_slot_ = -1, mixer_ctx_col_ = -1, ind_ctx_col_ = -1;
-  bool models_back_ = false, all_outputs_ = false;
+  bool models_back_ = false, all_outputs_ = false, ctx_values_ = false;
   uint64_t T_ = 0, round_ = 0, bits_submitted_ = 0;
   double submit_seconds_ = 0, wait_seconds_ = 0;
   const bool trace_ = getenv("GMX_POOL_TRACE") != nullptr;
   std::map<std::string, double> step_seconds_;
   std::vector<std::chrono::steady_clock::time_point> left_at_;  // (trace) when each stream last left Arrive
-  int n_pad_ = 0, mask_words_ = 0, M_ = 0, K_ = 0, KM_ = 0;
+  int n_pad_ = 0, mask_words_ = 0, M_ = 0, K_ = 0, KM_ = 0, V_ = 0;
   int participants_ = 0, arrived_ = 0;
   std::vector<uint64_t> n_cur_, n_in_[kRing], n_bytes_;
 };
@@ -929,6 +1035,7 @@ class GpuMixerBank {
   friend class GpuIndirectBank;
   friend class GpuLstmModel;
   friend class GpuMatchBank;
+  friend class GpuCtxBank;
   const unsigned int* MixerContextAddress(size_t j) const;
   GpuMixerBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
     pool_ = MixerPool::Attach(&ltm, &slot_);
@@ -1091,9 +1198,13 @@ class GpuMixerBank {
         for (size_t j = 0; j < descs_.size(); ++j) {
           if ((int)j == lstm_ctx_col_) continue;    // (that context is the device's: counted when its chunk returns)
           if (std::find(match_cols_.begin(), match_cols_.end(), (int32_t)j) != match_cols_.end()) continue;  // (likewise)
-          if (!first_mark_ && c[j] == last_ctx_[j]) continue;  // (most contexts stand for a whole byte)
-          last_ctx_[j] = c[j];
-          MarkSeen(j, c[j]);
+          if (ctx_obj_col_[j] >= 0) continue;       // (likewise: a context object on the device)
+          // (a field of BasicContexts that the context bank writes on the device is not recorded: the host's
+          // BasicContexts still computes it, so it is read where the mixer reads it)
+          const uint32_t cj = (s.croutes && s.croutes->mixers[j] >= 0) ? *MixerContextAddress(j) : c[j];
+          if (!first_mark_ && cj == last_ctx_[j]) continue;  // (most contexts stand for a whole byte)
+          last_ctx_[j] = cj;
+          MarkSeen(j, cj);
         }
         first_mark_ = false;
       }
@@ -1172,6 +1283,7 @@ class GpuMixerBank {
   uint64_t T_ = 0;
   int n_pad_ = 0, mask_words_ = 0, lstm_ctx_col_ = -1;
   std::vector<int32_t> match_cols_;  // gate-context columns the device fills with longest_match (run-ahead)
+  std::vector<int32_t> ctx_obj_col_; // [M] the context object (variable index) a gate context is, or -1 (run-ahead)
   std::vector<std::vector<uint64_t>> seen_;
   std::vector<uint32_t> last_ctx_;   // the context each mixer's row was last marked for
   std::vector<uint8_t> last_ind_active_;  // the Indirect models' active flags of the newest bit that came back
@@ -1280,6 +1392,7 @@ class GpuIndirectBank {
  private:
   friend class GpuIndirect;
   friend class GpuMixerBank;
+  friend class GpuCtxBank;
   GpuIndirectBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
     pool_ = MixerPool::Attach(&ltm, &slot_);
     std::lock_guard<std::mutex> lk(pool_->mu_);
@@ -1439,7 +1552,7 @@ class GpuIndirectBank {
     MixerPool::Stream& s = st();
     if (s.ls) return;  // (lock step: the mixers' Learn asks for the step's learn, which is every device-side model's)
     if (s.ra) {
-      s.ibits[s.t] = (uint8_t)stm.new_bit;  // Indirect::Learn x 41, recorded
+      if (!s.croutes) s.ibits[s.t] = (uint8_t)stm.new_bit;  // Indirect::Learn x 41, recorded (else: gmx_ctx_run_ragged's)
       return;
     }
     Call("gmx_indirect_learn", [&] { return gmx_indirect_learn(h_, slot_, stm.new_bit); });
@@ -1542,6 +1655,11 @@ inline void GpuIndirectBank::PredictAll(ShortTermMemory& stm) {
   MixerPool::Stream& s = st();
   if (s.ls) {  // lock step: the contexts into the step's records; the mixers' Predict, next in line, waits for the step
     uint32_t* c = gmx_chainstep_ind_contexts(pool_->cs_) + (size_t)slot_ * models_.size();
+    if (s.croutes) {  // (the context bank's stage writes its columns and bit_contexts on the device)
+      for (size_t i = 0; i < models_.size(); ++i)
+        if (s.croutes->indirect[i] < 0) c[i] = models_[i]->context();
+      return;
+    }
     for (size_t i = 0; i < models_.size(); ++i) c[i] = models_[i]->context();
     gmx_chainstep_bit_contexts(pool_->cs_)[slot_] = stm.bit_context;
     return;
@@ -1549,6 +1667,11 @@ inline void GpuIndirectBank::PredictAll(ShortTermMemory& stm) {
   if (s.ra) {
     // Indirect::Predict x 41, recorded: the contexts as they stand when the last model is called, bit_context
     uint32_t* c = s.ictx + (size_t)s.t * models_.size();
+    if (s.croutes) {  // (gmx_ctx_run_ragged writes its columns, bit_contexts and bits on the device)
+      for (size_t i = 0; i < models_.size(); ++i)
+        if (s.croutes->indirect[i] < 0) c[i] = models_[i]->context();
+      return;
+    }
     for (size_t i = 0; i < models_.size(); ++i) c[i] = models_[i]->context();
     s.ibc[s.t] = stm.bit_context;
     return;
@@ -1858,6 +1981,7 @@ class GpuMatchBank {
  private:
   friend class GpuMatch;
   friend class GpuMixerBank;
+  friend class GpuCtxBank;
   GpuMatchBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
     pool_ = MixerPool::Attach(&ltm, &slot_);
     std::lock_guard<std::mutex> lk(pool_->mu_);
@@ -2035,7 +2159,7 @@ class GpuMatchBank {
     if (s.ls || s.ra) ltm_.history.clear();  // (what BasicContexts::Learn has just pushed: the bank keeps the history)
     if (s.ls) return;  // (lock step: the mixers' Learn asks for the step's learn, which is every device-side model's)
     if (s.ra) {
-      s.mbits[s.t] = (uint8_t)stm.new_bit;  // the history push of BasicContexts::Learn + Match::Learn x 6, recorded
+      if (!s.croutes) s.mbits[s.t] = (uint8_t)stm.new_bit;  // the history push of BasicContexts::Learn + Match::Learn x 6, recorded
       return;
     }
     if (!fwd_pending_) return;  // (a Learn without its Predict: nothing was predicted to learn from)
@@ -2130,6 +2254,7 @@ class GpuMatch : public Model {
     return v;
   }
   unsigned int context() const { return byte_context_; }
+  const unsigned int* context_address() const { return &byte_context_; }
 
  private:
   const unsigned int& byte_context_;  // aliases a field of the Predictor's blackboard (match.h:33)
@@ -2145,16 +2270,22 @@ inline void GpuMatchBank::PredictAll(ShortTermMemory& stm) {
   if (s.ls) {
     // lock step: bit_context on every predict; the contexts when a byte opens and on the stream's first predict
     // through the object (gmx_chainstep_attach_match).  The mixers' Predict, last in line, waits for the step.
-    gmx_chainstep_bit_contexts(pool_->cs_)[slot_] = stm.bit_context;
+    if (!s.croutes) gmx_chainstep_bit_contexts(pool_->cs_)[slot_] = stm.bit_context;
     if (ls_fresh_ || stm.bit_context == 0) {
       uint32_t* c = gmx_chainstep_match_contexts(pool_->cs_) + (size_t)slot_ * models_.size();
-      for (size_t i = 0; i < models_.size(); ++i) c[i] = models_[i]->context();
+      for (size_t i = 0; i < models_.size(); ++i)
+        if (!s.croutes || s.croutes->match[i] < 0) c[i] = models_[i]->context();
       ls_fresh_ = false;
     }
     return;
   }
   if (s.ra) {  // Match::Predict x 6, recorded
     uint32_t* c = s.mctx + (size_t)s.t * models_.size();
+    if (s.croutes) {
+      for (size_t i = 0; i < models_.size(); ++i)
+        if (s.croutes->match[i] < 0) c[i] = models_[i]->context();
+      return;
+    }
     for (size_t i = 0; i < models_.size(); ++i) c[i] = models_[i]->context();
     s.mbc[s.t] = stm.bit_context;
     return;
@@ -2186,6 +2317,559 @@ inline void GpuMatchBank::PredictAll(ShortTermMemory& stm) {
   }
   stm.longest_match = std::max(stm.longest_match, (unsigned int)longest);
 }
+
+// ================================================================================================
+// `gmx::GpuIntervalContext`, `gmx::GpuSkipContext` and `gmx::GpuIndirectHash` with the constructor signatures of
+// IntervalContext (contexts/interval-context.h:18-19), SkipContext (skip-context.h:16-17) and IndirectHash
+// (indirect-hash.h:15-16): the 38 context objects of the reference's Predictor as one stream of a gmx_ctx bank, which
+// computes them -- and its own copy of BasicContexts' fields -- from the coded bits alone.  Switched in like the others
+// (`new IntervalContext(` x 9, `new SkipContext(` x 20, `new IndirectHash(` x 9, and `new BasicContexts(` ->
+// `new gmx::GpuBasicContexts(` once; dropin/Makefile builds gmix_dev / ref_tester_dev that way), the Predictor keeps
+// no hash table on the host (201 MB for the stock nine) and computes no MurmurHash3.
+//
+// The host's BasicContexts stays: PPMd and the LSTM adapter read its fields, and it is cheap.  GpuBasicContexts is
+// BasicContexts plus a readable copy of first_prediction_, which the bank's blackboard needs and the reference keeps
+// private.
+//
+// The objects are constructed with nothing but their output field, so they find their bank by ITS ADDRESS: it lies
+// inside the ShortTermMemory the Predictor's GpuMixer objects were constructed with (GpuMixerBank's registry).  That is
+// settled at the first call of any method of any of them -- Predictor's constructor has finished by then -- and with it
+// the descriptor list and the routes: every registered object is a variable, in construction order; every context
+// address a GpuMixer, GpuIndirect or GpuMatch of the Predictor reads is looked up among the objects' output fields and
+// BasicContexts' fields (which become variables behind the objects', in gmxmix.h's order of kinds); longest_match,
+// lstm_prediction_context and any address nobody registered stay the host's (-1).  For the stock Predictor that is
+// gmix_amd.topology.stock_contexts(): 52 variables.
+//
+// Per bit, the first object's Predict runs gmx_ctx_forward once and writes every object's value into its
+// ShortTermMemory field, so everything downstream reads the blackboard as it does in the reference.  Running ahead the
+// bank's only record is the coded bit (MixerPool::Lead: gmx_ctx_run_ragged in front of the Match bank's run, writing the
+// routed columns of the three record batches); in lock step it is a stage of the step (gmx_chainstep_attach_ctx).  In
+// those two modes the objects' ShortTermMemory fields go stale; they come home with the other banks' slots
+// (GpuMixerBank::SlotsHome).
+// ================================================================================================
+// Construction order of GpuBasicContexts and the context objects ON THIS THREAD (a Predictor is built on one thread;
+// Predictors of a pool may be built side by side on several).
+inline uint64_t NextCtxSeq() {
+  static thread_local uint64_t n = 0;
+  return n++;
+}
+class GpuBasicContexts : public BasicContexts {
+ public:
+  GpuBasicContexts() : seq_(NextCtxSeq()) { LastOnThisThread() = this; }
+  uint64_t seq() const { return seq_; }  // construction order among the context classes
+  ~GpuBasicContexts() override {
+    if (LastOnThisThread() == this) LastOnThisThread() = nullptr;
+  }
+  // A board that waits to be made from the ShortTermMemory (after ReadCheckpoint or Copy) is made BEFORE this bit is
+  // folded into it: the bank folds the bit itself (gmx_ctx_forward).
+  void Predict(ShortTermMemory& short_term_memory, const LongTermMemory& long_term_memory) override;
+  void ReadFromDisk(std::ifstream* s) override {  // basic-contexts.cpp:59-61: one byte
+    const int c = s->peek();
+    if (c != std::char_traits<char>::eof()) first_prediction_ = c != 0;
+    BasicContexts::ReadFromDisk(s);
+  }
+  void Copy(const MemoryInterface* m) override {
+    BasicContexts::Copy(m);
+    first_prediction_ = static_cast<const GpuBasicContexts*>(m)->first_prediction_;
+  }
+  bool first_prediction() const { return first_prediction_; }
+  // Predictor's constructor builds BasicContexts first and the context objects behind it, on one thread
+  // (predictor.cpp:17-28): an object takes the BasicContexts of its Predictor from here.
+  static GpuBasicContexts*& LastOnThisThread() {
+    static thread_local GpuBasicContexts* p = nullptr;
+    return p;
+  }
+
+ private:
+  bool first_prediction_ = true;  // shadows BasicContexts::first_prediction_
+  const uint64_t seq_;
+  GpuCtxBank* bank_ = nullptr;    // the Predictor's context bank, once looked for (null: it has no device context objects)
+  bool bank_known_ = false;
+};
+
+// What the three classes share: the output field, the variable's description and the way to the bank.
+class GpuCtxVar : public Model {
+ public:
+  ~GpuCtxVar() override {
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    auto it = Pending().find(&out_);
+    if (it != Pending().end() && it->second == this) Pending().erase(it);
+  }
+  void Predict(ShortTermMemory& short_term_memory, const LongTermMemory&) override;
+  void Learn(const ShortTermMemory& short_term_memory, LongTermMemory&) override;
+  void WriteToDisk(std::ofstream*) override {}  // interval-context.h:24, skip-context.h:22: nothing
+  void ReadFromDisk(std::ifstream*) override;
+  void Copy(const MemoryInterface* m) override;
+  unsigned long long GetMemoryUsage(const ShortTermMemory&, const LongTermMemory&) override;
+  const unsigned int* output_address() const { return &out_; }
+
+ protected:
+  friend class GpuCtxBank;
+  explicit GpuCtxVar(unsigned int& output_context) : out_(output_context), basic_(GpuBasicContexts::LastOnThisThread()) {
+    memset(&desc_, 0, sizeof desc_);
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    seq_ = NextCtxSeq();
+    Pending()[&out_] = this;
+  }
+  GpuCtxBank* Bank();
+  static std::map<const unsigned int*, GpuCtxVar*>& Pending() {  // every live object by its output field
+    static std::map<const unsigned int*, GpuCtxVar*> r;
+    return r;
+  }
+
+  unsigned int& out_;  // aliases a field of the Predictor's blackboard
+  gmx_ctx_desc desc_;
+  std::string bad_;  // why gmx_ctx_create could not take this object, if it could not
+  GpuBasicContexts* basic_;
+  uint64_t seq_ = 0;
+  std::shared_ptr<GpuCtxBank> bank_;
+  int var_ = -1;   // the variable's index in the bank
+  int hash_ = -1;  // ... and among the bank's hash variables
+};
+
+// All context objects of one Predictor: one stream of a gmx_ctx (the Predictor's own, or a MixerPool's).
+class GpuCtxBank {
+ public:
+  // The bank of the Predictor whose ShortTermMemory holds `addr`.
+  static std::shared_ptr<GpuCtxBank> ForAddress(const unsigned int* addr) {
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    std::shared_ptr<GpuMixerBank> mixers;
+    for (auto& kv : GpuMixerBank::Registry()) {
+      auto sp = kv.second.lock();
+      if (!sp) continue;
+      const char* lo = reinterpret_cast<const char*>(&sp->stm());
+      const char* a = reinterpret_cast<const char*>(addr);
+      if (a >= lo && a < lo + sizeof(ShortTermMemory)) mixers = sp;
+    }
+    if (!mixers) {
+      fprintf(stderr, "\ngmx::GpuCtxBank: a context object's output field lies in no ShortTermMemory a gmx::GpuMixer was "
+                      "constructed with (the device context bank needs the mixers on the device: INTEGRATION.md section 2)\n");
+      abort();
+    }
+    auto& reg = Registry();
+    auto it = reg.find(&mixers->ltm());
+    if (it != reg.end())
+      if (auto sp = it->second.lock()) return sp;
+    std::shared_ptr<GpuCtxBank> sp(new GpuCtxBank(mixers->stm(), mixers->ltm()));
+    reg[&mixers->ltm()] = sp;
+    // every object whose output field lies in this ShortTermMemory, in construction order
+    const unsigned int* lo = reinterpret_cast<const unsigned int*>(&sp->stm_);
+    const unsigned int* hi = reinterpret_cast<const unsigned int*>(reinterpret_cast<const char*>(&sp->stm_) + sizeof(ShortTermMemory));
+    auto& pend = GpuCtxVar::Pending();
+    for (auto p = pend.lower_bound(lo); p != pend.end() && p->first < hi; ++p) sp->vars_.push_back(p->second);
+    std::sort(sp->vars_.begin(), sp->vars_.end(), [](const GpuCtxVar* a, const GpuCtxVar* b) { return a->seq_ < b->seq_; });
+    int h = 0;
+    for (size_t i = 0; i < sp->vars_.size(); ++i) {
+      sp->vars_[i]->bank_ = sp;
+      sp->vars_[i]->var_ = (int)i;
+      if (sp->vars_[i]->desc_.kind == GMX_CTX_INDIRECT_HASH) sp->vars_[i]->hash_ = h++;
+    }
+    sp->n_hash_ = h;
+    sp->basic_ = sp->vars_.empty() ? nullptr : sp->vars_[0]->basic_;
+    return sp;
+  }
+  ~GpuCtxBank() {
+    {
+      std::lock_guard<std::mutex> lk(pool_->mu_);
+      st().cbank = nullptr;
+    }
+    pool_->Detach(slot_);
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    Registry().erase(&ltm_);
+  }
+  GpuCtxBank(const GpuCtxBank&) = delete;
+  GpuCtxBank& operator=(const GpuCtxBank&) = delete;
+
+  // The bank of the Predictor that owns `stm`, settled now if no object of it has been called yet; null when the
+  // Predictor has no device context objects.
+  static GpuCtxBank* Resolve(const ShortTermMemory& stm);
+  const CtxRoutes& routes() const { return routes_; }
+  int n_vars() const { return (int)descs_.size(); }
+  int n_objects() const { return (int)vars_.size(); }  // variables [0, n_objects) are the Predictor's context objects
+
+ private:
+  friend class GpuCtxVar;
+  friend class GpuIndirectHash;
+  friend class GpuMixerBank;
+  friend class GpuBasicContexts;
+  GpuCtxBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
+    pool_ = MixerPool::Attach(&ltm, &slot_);
+    std::lock_guard<std::mutex> lk(pool_->mu_);
+    st().cbank = this;
+  }
+  static std::map<const LongTermMemory*, std::weak_ptr<GpuCtxBank>>& Registry() {
+    static std::map<const LongTermMemory*, std::weak_ptr<GpuCtxBank>> r;
+    return r;
+  }
+  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
+  template <class F>
+  void Call(const char* what, F f) {
+    pool_->Call("gmx::GpuCtxBank", what, f);
+  }
+  [[noreturn]] static void Refuse(const std::string& why) {
+    fprintf(stderr, "\ngmx::GpuCtxBank: %s\n(the context objects of this Predictor cannot be described to gmx_ctx_create; "
+                    "there is no CPU fallback)\n", why.c_str());
+    abort();
+  }
+  // The variable a sink's context address receives: an object's output field, a field of BasicContexts (made a
+  // variable on first use), or -1 -- the column stays the host's (or another device-side writer's).
+  int Lookup(const unsigned int* addr, std::vector<int>& basic_var) {
+    for (size_t i = 0; i < vars_.size(); ++i)
+      if (vars_[i]->output_address() == addr) return (int)i;
+    // gmxmix.h's kinds in topology.stock_context_descs()' order: RECENT_BYTE 0..9, BIT_CONTEXT, BYTE_PLUS_RECENT 0 / 1, ZERO
+    int k = -1;
+    if (addr == &stm_.last_byte) k = 0;
+    for (size_t i = 0; i < stm_.recent_bytes.size() && i < 10; ++i)
+      if (addr == &stm_.recent_bytes[i]) k = (int)i;
+    if (addr == &stm_.bit_context) k = 10;
+    if (addr == &stm_.last_byte_plus_recent) k = 11;
+    if (addr == &stm_.second_last_plus_recent) k = 12;
+    if (addr == &stm_.always_zero) k = 13;
+    if (k < 0) return -1;
+    basic_var[k] = 1;
+    return -2 - k;  // resolved when every sink has been looked at
+  }
+  // Descriptors and routes from what the constructors registered (all of them have run by the time any method of a
+  // model is called), and the device bank.
+  void Ensure() {
+    if (h_) return;
+    if (!basic_)
+      Refuse("the Predictor's BasicContexts is not gmx::GpuBasicContexts (the fourth switch of the *_dev builds: `new "
+             "BasicContexts(` -> `new gmx::GpuBasicContexts(`)");
+    // Predictor's constructor builds BasicContexts and then, on the same thread, the first context object
+    // (predictor.cpp:19-20): anything else in between means the thread-local handed over another Predictor's
+    if (vars_.empty() || basic_->seq() + 1 != vars_[0]->seq_)
+      Refuse("the GpuBasicContexts found for this Predictor was not constructed right in front of its first context "
+             "object: all four switches of the *_dev builds go together");
+    for (GpuCtxVar* v : vars_)
+      if (!v->bad_.empty()) Refuse(v->bad_);
+    MixerPool::Stream& s = st();
+    std::vector<int> basic_var(14, 0);
+    CtxRoutes r;
+    if (s.mixers)
+      for (size_t j = 0; j < s.mixers->mixers_.size(); ++j) r.mixers.push_back(Lookup(s.mixers->MixerContextAddress(j), basic_var));
+    if (s.indirect)
+      for (GpuIndirect* m : s.indirect->models_) r.indirect.push_back(Lookup(m->context_address(), basic_var));
+    if (s.match)
+      for (GpuMatch* m : s.match->models_) r.match.push_back(Lookup(m->context_address(), basic_var));
+    descs_.clear();
+    for (GpuCtxVar* v : vars_) descs_.push_back(v->desc_);
+    std::vector<int> basic_index(14, -1);
+    for (int k = 0; k < 14; ++k) {
+      if (!basic_var[k]) continue;
+      gmx_ctx_desc d;
+      memset(&d, 0, sizeof d);
+      d.kind = k < 10 ? GMX_CTX_RECENT_BYTE : k == 10 ? GMX_CTX_BIT_CONTEXT : k < 13 ? GMX_CTX_BYTE_PLUS_RECENT : GMX_CTX_ZERO;
+      d.index = k < 10 ? k : k == 12 ? 1 : 0;
+      basic_index[k] = (int)descs_.size();
+      descs_.push_back(d);
+    }
+    for (std::vector<int32_t>* route : {&r.mixers, &r.indirect, &r.match})
+      for (int32_t& e : *route)
+        if (e <= -2) e = basic_index[-2 - e];
+    routes_ = r;
+    if (descs_.size() > 64) Refuse("more than 64 context variables (" + std::to_string(descs_.size()) + ")");
+    if (n_hash_ > 16) Refuse("more than 16 IndirectHash objects (" + std::to_string(n_hash_) + ")");
+    if (getenv("GMX_CTX_DESCRIBE")) Describe();
+    Call("gmx_ctx_create", [&] { return pool_->EnsureCtx(descs_); });
+    h_ = pool_->ctx();
+    values_.assign(descs_.size(), 0u);
+    if (pool_->status()) return;
+    bool used;
+    {
+      std::lock_guard<std::mutex> lk(pool_->mu_);
+      used = pool_->ctx_used_[slot_] != 0;
+      pool_->ctx_used_[slot_] = 1;
+    }
+    if (used) {  // the stream served another Predictor: empty tables, and the board of this one
+      std::vector<char> empty;  // per hash object: a count of 0, a table of one entry whole (indirect-hash.cpp:41), 12 state bytes
+      for (GpuCtxVar* v : vars_)
+        if (v->hash_ >= 0) empty.resize(empty.size() + 4 + (v->desc_.table_size / 2 > 0 ? 0 : 4 * (size_t)v->desc_.table_size) + 12, 0);
+      if (n_hash_) Call("gmx_ctx_import", [&] { return gmx_ctx_import(h_, slot_, empty.data(), empty.size()); });
+      board_pending_ = true;
+    }
+  }
+  // GMX_CTX_DESCRIBE=1: what was derived, one line per variable and route (tests/test_dev_cpu.py compares it with
+  // gmix_amd.topology.stock_contexts())
+  void Describe() const {
+    for (size_t i = 0; i < descs_.size(); ++i) {
+      const gmx_ctx_desc& d = descs_[i];
+      fprintf(stderr, "[gmx ctx] var %zu kind %d index %d num_bits %d n_bytes %d outer %d inner %d table %u bytes", i, d.kind,
+              d.index, d.num_bits, d.n_bytes, d.outer_order, d.inner_order, d.table_size);
+      for (int k = 0; k < d.n_bytes; ++k) fprintf(stderr, " %d", d.bytes_to_use[k]);
+      fprintf(stderr, " map_div %d\n", d.kind == GMX_CTX_INTERVAL ? (d.map[255] ? 256 / (d.map[255] + 1) : 0) : 0);
+    }
+    const char* names[3] = {"mixer", "indirect", "match"};
+    const std::vector<int32_t>* rs[3] = {&routes_.mixers, &routes_.indirect, &routes_.match};
+    for (int k = 0; k < 3; ++k) {
+      fprintf(stderr, "[gmx ctx] route %s", names[k]);
+      for (int32_t e : *rs[k]) fprintf(stderr, " %d", e);
+      fprintf(stderr, "\n");
+    }
+  }
+  void SyncIfAhead() {
+    MixerPool::Stream& s = st();
+    if (s.ra && s.mixers) s.mixers->SyncRunAhead();
+  }
+  // Ensure, then what a ReadCheckpoint or a Copy left to do: the hash sections read from the .short stream go to the
+  // device, and the board is built from the ShortTermMemory as it stands now (restored, or copied -- ShortTermMemory's
+  // serialiser and Copy both skip last_two_bytes_hash, short-term-memory.cpp:3-59, :119-176: the field keeps the value
+  // this Predictor had, and the board takes it from there) and the shadowed first_prediction_.
+  void Settle() {
+    Ensure();
+    if (!import_pending_ && !board_pending_) return;
+    if (pool_->status()) return;
+    SyncIfAhead();
+    if (import_pending_) {
+      import_pending_ = false;
+      Call("gmx_ctx_import", [&] { return gmx_ctx_import(h_, slot_, import_buf_.data(), import_buf_.size()); });
+      std::vector<char>().swap(import_buf_);
+    }
+    board_pending_ = false;
+    gmx_ctx_blackboard bb;
+    memset(&bb, 0, sizeof bb);
+    bb.recent_bits = stm_.recent_bits;
+    bb.new_bit = stm_.new_bit ? 1 : 0;
+    bb.last_byte = stm_.last_byte;
+    bb.rotating_history_pos = stm_.rotating_history_pos;
+    bb.first_prediction = basic_->first_prediction() ? 1 : 0;
+    for (size_t i = 0; i < 10 && i < stm_.recent_bytes.size(); ++i) bb.recent_bytes[i] = stm_.recent_bytes[i];
+    for (size_t i = 0; i < 1000 && i < stm_.rotating_history.size(); ++i) bb.rotating_history[i] = stm_.rotating_history[i];
+    for (size_t v = 0; v < descs_.size(); ++v) {
+      const gmx_ctx_desc& d = descs_[v];
+      if (v < vars_.size())
+        bb.values[v] = vars_[v]->out_;
+      else if (d.kind == GMX_CTX_RECENT_BYTE)
+        bb.values[v] = bb.recent_bytes[d.index];
+      else if (d.kind == GMX_CTX_BIT_CONTEXT)
+        bb.values[v] = (uint32_t)bb.recent_bits - 1;
+      else if (d.kind == GMX_CTX_BYTE_PLUS_RECENT)
+        bb.values[v] = (bb.recent_bytes[d.index] << 8) + (uint32_t)bb.recent_bits - 1;
+    }
+    Call("gmx_ctx_blackboard_set", [&] { return gmx_ctx_blackboard_set(h_, slot_, &bb); });
+    forwarded_ = false;  // (a new board drops a pending forward; its new_bit is the bit coded since)
+    learned_ = true;
+  }
+  // BasicContexts' fields, IntervalContext x 9, SkipContext x 20 and IndirectHash x 9 of one bit
+  void PredictAll(ShortTermMemory& stm) {
+    Settle();
+    if (pool_->status()) return;
+    MixerPool::Stream& s = st();
+    if (s.ls || s.ra) return;  // the step's first stage / gmx_ctx_run_ragged over the chunk's recorded bits
+    if (!learned_)  // a bit that was only perceived (generation, tester.cpp:296-302): what BasicContexts::Predict folds
+      Call("gmx_ctx_learn", [&] { return gmx_ctx_learn(h_, slot_, stm.new_bit ? 1 : 0); });
+    learned_ = false;
+    Call("gmx_ctx_forward", [&] { return gmx_ctx_forward(h_, slot_, values_.data(), nullptr); });
+    if (pool_->status()) return;
+    forwarded_ = true;
+    for (size_t i = 0; i < vars_.size(); ++i) vars_[i]->out_ = values_[i];
+  }
+  void LearnAll(const ShortTermMemory& stm) {
+    Settle();
+    if (pool_->status()) return;
+    MixerPool::Stream& s = st();
+    learned_ = true;
+    if (s.ls) return;  // (lock step: the mixers' Learn hands the step its bit, which is every device-side model's)
+    if (s.ra) {
+      s.cbits[s.t] = (uint8_t)(stm.new_bit ? 1 : 0);  // the whole record of this bank
+      return;
+    }
+    forwarded_ = false;
+    Call("gmx_ctx_learn", [&] { return gmx_ctx_learn(h_, slot_, stm.new_bit ? 1 : 0); });
+  }
+  // A stream that stands between a forward and its learn (a Predict whose bit was perceived, not learned) is settled
+  // with the bit the next Predict would fold anyway: the runs, the lock step and gmx_ctx_copy refuse it otherwise.
+  void SettleForward() {
+    if (!forwarded_ || learned_) return;
+    Call("gmx_ctx_learn", [&] { return gmx_ctx_learn(h_, slot_, stm_.new_bit ? 1 : 0); });
+    forwarded_ = false;
+    learned_ = true;
+  }
+  // The objects' ShortTermMemory fields as the device left them (after run-ahead or lock step)
+  void HomeFromDevice() {
+    if (!h_) return;
+    gmx_ctx_blackboard bb;
+    Call("gmx_ctx_blackboard_get", [&] { return gmx_ctx_blackboard_get(h_, slot_, &bb); });
+    if (pool_->status()) return;
+    for (size_t i = 0; i < vars_.size(); ++i) vars_[i]->out_ = bb.values[i];
+    forwarded_ = false;
+    learned_ = true;
+  }
+  // One gmx_ctx_export per checkpoint: the first hash object fetches the sections of all of them.
+  void Stage() {
+    Settle();
+    SyncIfAhead();
+    size_t n = 0;
+    export_off_.assign((size_t)n_hash_ + 1, 0);
+    Call("gmx_ctx_export", [&] { return gmx_ctx_export(h_, slot_, nullptr, &n, export_off_.data()); });
+    export_buf_.assign(n ? n : 1, 0);
+    Call("gmx_ctx_export", [&] { return gmx_ctx_export(h_, slot_, export_buf_.data(), &n, export_off_.data()); });
+  }
+  void CopyFrom(GpuCtxBank& o) {
+    o.Settle();
+    o.SyncIfAhead();
+    o.SettleForward();
+    Ensure();
+    SyncIfAhead();
+    import_pending_ = false;
+    if (o.pool_ == pool_) {
+      Call("gmx_ctx_copy", [&] { return gmx_ctx_copy(h_, slot_, o.h_, o.slot_); });
+    } else {  // two banks: both pools' calls held off, always in address order
+      MixerPool* a = pool_.get() < o.pool_.get() ? pool_.get() : o.pool_.get();
+      MixerPool* b = pool_.get() < o.pool_.get() ? o.pool_.get() : pool_.get();
+      int rc;
+      {
+        std::lock_guard<std::mutex> la(a->mu_);
+        std::lock_guard<std::mutex> lb(b->mu_);
+        rc = gmx_ctx_copy(h_, slot_, o.h_, o.slot_);
+      }
+      pool_->Check("gmx::GpuCtxBank", "gmx_ctx_copy", rc);
+    }
+    // ShortTermMemory::Copy follows (predictor.cpp:42-48) and is not quite a copy (last_two_bytes_hash stays): the board
+    // is made from this Predictor's own ShortTermMemory at the next call, as after a ReadCheckpoint
+    board_pending_ = true;
+  }
+
+  ShortTermMemory& stm_;
+  LongTermMemory& ltm_;
+  std::shared_ptr<MixerPool> pool_;
+  int slot_ = 0;
+  gmx_ctx* h_ = nullptr;
+  GpuBasicContexts* basic_ = nullptr;
+  std::vector<GpuCtxVar*> vars_;  // the objects, in construction order: variables [0, vars_.size())
+  int n_hash_ = 0;
+  std::vector<gmx_ctx_desc> descs_;
+  CtxRoutes routes_;
+  std::vector<uint32_t> values_;
+  std::vector<char> import_buf_, export_buf_;
+  std::vector<size_t> export_off_;
+  bool import_pending_ = false, board_pending_ = false;
+  bool learned_ = false;    // the board's new_bit is the newest coded bit
+  bool forwarded_ = false;  // per bit: a gmx_ctx_forward waits for its learn
+};
+
+inline GpuCtxBank* GpuCtxVar::Bank() {
+  if (!bank_) {
+    std::shared_ptr<GpuCtxBank> sp = GpuCtxBank::ForAddress(&out_);  // (sets bank_ of every object of the Predictor)
+    if (!bank_) {  // constructed after the bank was settled: not a Predictor the reference builds
+      fprintf(stderr, "\ngmx::GpuCtxBank: a context object was constructed after its Predictor's first call\n");
+      abort();
+    }
+  }
+  return bank_.get();
+}
+inline GpuCtxBank* GpuCtxBank::Resolve(const ShortTermMemory& stm) {
+  GpuCtxVar* any = nullptr;
+  {
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    const unsigned int* lo = reinterpret_cast<const unsigned int*>(&stm);
+    const unsigned int* hi = reinterpret_cast<const unsigned int*>(reinterpret_cast<const char*>(&stm) + sizeof(ShortTermMemory));
+    auto& pend = GpuCtxVar::Pending();
+    auto p = pend.lower_bound(lo);
+    if (p != pend.end() && p->first < hi) any = p->second;
+  }
+  return any ? any->Bank() : nullptr;
+}
+inline void GpuBasicContexts::Predict(ShortTermMemory& short_term_memory, const LongTermMemory& long_term_memory) {
+  if (!bank_known_) {
+    bank_ = GpuCtxBank::Resolve(short_term_memory);
+    bank_known_ = true;
+  }
+  if (bank_) bank_->Settle();
+  BasicContexts::Predict(short_term_memory, long_term_memory);
+  first_prediction_ = false;  // basic-contexts.cpp:23-27
+}
+inline void GpuCtxVar::Predict(ShortTermMemory& short_term_memory, const LongTermMemory&) {
+  if (Bank() && var_ == 0) bank_->PredictAll(short_term_memory);
+}
+inline void GpuCtxVar::Learn(const ShortTermMemory& short_term_memory, LongTermMemory&) {
+  if (Bank() && var_ == 0) bank_->LearnAll(short_term_memory);
+}
+inline void GpuCtxVar::ReadFromDisk(std::ifstream*) {
+  // ShortTermMemory::ReadFromDisk comes next (predictor.cpp:412-415): the board follows it at the next call
+  Bank()->board_pending_ = true;
+}
+inline void GpuCtxVar::Copy(const MemoryInterface* m) {
+  GpuCtxVar* orig = const_cast<GpuCtxVar*>(static_cast<const GpuCtxVar*>(m));
+  if (Bank() && var_ == 0) bank_->CopyFrom(*orig->Bank());
+}
+inline unsigned long long GpuCtxVar::GetMemoryUsage(const ShortTermMemory&, const LongTermMemory&) {
+  Bank()->Ensure();
+  uint64_t v = 0;
+  bank_->Call("gmx_ctx_memory_usage", [&] { return gmx_ctx_memory_usage(bank_->h_, var_, &v); });
+  return v;
+}
+
+class GpuIntervalContext : public GpuCtxVar {
+ public:
+  // contexts/interval-context.h:18-19, argument for argument.
+  GpuIntervalContext(const std::vector<int>& map, unsigned int num_bits, unsigned int& output_context)
+      : GpuCtxVar(output_context) {
+    output_context = 0;  // interval-context.cpp:7
+    desc_.kind = GMX_CTX_INTERVAL;
+    desc_.num_bits = (int32_t)num_bits;
+    if (map.size() != 256) bad_ = "an IntervalContext whose map has " + std::to_string(map.size()) + " entries, not 256";
+    for (size_t i = 0; i < map.size() && i < 256; ++i) {
+      if (map[i] < 0 || map[i] > 255) bad_ = "an IntervalContext whose map has a state outside 0..255";
+      desc_.map[i] = (uint8_t)map[i];
+    }
+    if (num_bits < 1 || num_bits > 31) bad_ = "an IntervalContext with num_bits " + std::to_string(num_bits) + " (1..31)";
+  }
+};
+
+class GpuSkipContext : public GpuCtxVar {
+ public:
+  // contexts/skip-context.h:16-17, argument for argument.
+  GpuSkipContext(const std::vector<int>& bytes_to_use, unsigned int& output_context) : GpuCtxVar(output_context) {
+    desc_.kind = GMX_CTX_SKIP;
+    desc_.n_bytes = (int32_t)bytes_to_use.size();
+    if (bytes_to_use.empty() || bytes_to_use.size() > 8)
+      bad_ = "a SkipContext over " + std::to_string(bytes_to_use.size()) + " bytes (1..8)";
+    for (size_t i = 0; i < bytes_to_use.size() && i < 8; ++i) {
+      if (bytes_to_use[i] < 0 || bytes_to_use[i] > 15) bad_ = "a SkipContext that reaches back " + std::to_string(bytes_to_use[i]) + " bytes (0..15)";
+      desc_.bytes_to_use[i] = (uint8_t)bytes_to_use[i];
+    }
+  }
+};
+
+class GpuIndirectHash : public GpuCtxVar {
+ public:
+  // contexts/indirect-hash.h:15-16, argument for argument.
+  GpuIndirectHash(int outer_order, unsigned int table_size, int inner_order, unsigned int& output_context)
+      : GpuCtxVar(output_context) {
+    desc_.kind = GMX_CTX_INDIRECT_HASH;
+    desc_.outer_order = outer_order;
+    desc_.inner_order = inner_order;
+    desc_.table_size = table_size;
+    if (outer_order < 1 || outer_order > 4 || inner_order < 1 || inner_order > 4 || table_size < 1)
+      bad_ = "an IndirectHash(" + std::to_string(outer_order) + ", " + std::to_string(table_size) + ", " +
+             std::to_string(inner_order) + ") (orders 1..4, table_size >= 1)";
+  }
+  // indirect-hash.cpp:33-54: the object's own section of the .short stream, from the bank's one export
+  void WriteToDisk(std::ofstream* s) override {
+    GpuCtxBank* b = Bank();
+    if (hash_ == 0) b->Stage();
+    if (b->pool_->status()) return;
+    s->write(b->export_buf_.data() + b->export_off_[hash_], (std::streamsize)(b->export_off_[hash_ + 1] - b->export_off_[hash_]));
+    if (hash_ + 1 == b->n_hash_) std::vector<char>().swap(b->export_buf_);
+  }
+  // indirect-hash.cpp:56-74: the count, the branch by table_size / 2, the 12 state bytes -- into staging; the bank imports
+  // all sections at the next call of any method, which is after ShortTermMemory::ReadFromDisk
+  void ReadFromDisk(std::ifstream* s) override {
+    GpuCtxBank* b = Bank();
+    if (hash_ == 0) b->import_buf_.clear();
+    std::vector<char>& buf = b->import_buf_;
+    uint32_t count = 0;
+    s->read(reinterpret_cast<char*>(&count), 4);
+    const size_t body = count < desc_.table_size / 2 ? 8 * (size_t)count : 4 * (size_t)desc_.table_size;
+    const size_t at = buf.size();
+    buf.resize(at + 4 + body + 12);
+    memcpy(&buf[at], &count, 4);
+    s->read(&buf[at + 4], (std::streamsize)(body + 12));
+    b->import_pending_ = true;
+    b->board_pending_ = true;
+  }
+};
 
 // ---- the parts of the mixers' bank that know the other two ---------------------------------------------------
 inline void GpuMatchBank::SyncIfAhead() {
@@ -2257,12 +2941,26 @@ inline int GpuMixerBank::BeginRunAhead(RunAheadSink* sink, uint64_t chunk_bits) 
     parts |= MixerPool::kMatch;
     match_cols = MatchColumns();
   }
+  CtxRoutes ctx_routes;
+  GpuCtxBank::Resolve(stm_);  // (a Predictor none of whose context objects has been called yet)
+  if (s.cbank) {
+    s.cbank->Settle();
+    s.cbank->SettleForward();
+    parts |= MixerPool::kCtx;
+    ctx_routes = s.cbank->routes();
+  }
   if (status()) return status();
   match_cols_ = match_cols;
   lstm_ctx_col_ = mixer_ctx_col;
   // rows this bank has seen (Mixer::contexts_seen_ / GetMemoryUsage while the device runs behind), when the sink
   // will ask: 33 modulos and bitmap words per bit otherwise spent for nothing
   track_seen_ = sink && sink->WantsMemoryUsage();
+  // gate contexts that are context OBJECTS on the device: the host's fields are stale while it runs ahead, their rows
+  // are counted from the values that come back with the chunk (BasicContexts' fields the host still computes itself)
+  ctx_obj_col_.assign(descs_.size(), -1);
+  if (s.cbank)
+    for (size_t j = 0; j < descs_.size() && j < ctx_routes.mixers.size(); ++j)
+      if (ctx_routes.mixers[j] >= 0 && ctx_routes.mixers[j] < s.cbank->n_objects()) ctx_obj_col_[j] = ctx_routes.mixers[j];
   seen_.assign(descs_.size(), std::vector<uint64_t>());
   seen_count_.assign(descs_.size(), 0);
   last_ctx_.assign(descs_.size(), 0);
@@ -2281,7 +2979,7 @@ inline int GpuMixerBank::BeginRunAhead(RunAheadSink* sink, uint64_t chunk_bits) 
     Unstage();
   }
   int rc = pool_->Join(slot_, chunk_bits, parts, lstm_slot, mixer_ctx_col, ind_ctx_col, sink && sink->WantsModels(),
-                       sink && sink->WantsAllOutputs(), match_cols);
+                       sink && sink->WantsAllOutputs(), match_cols, ctx_routes);
   if (rc) return rc;
   T_ = pool_->chunk_bits();
   n_pad_ = pool_->n_pad_;
@@ -2322,10 +3020,18 @@ inline int GpuMixerBank::BeginLockstep() {
     parts |= MixerPool::kMatch;
     match_cols = MatchColumns();
   }
+  CtxRoutes ctx_routes;
+  GpuCtxBank::Resolve(stm_);  // (a Predictor none of whose context objects has been called yet)
+  if (s.cbank) {
+    s.cbank->Settle();
+    s.cbank->SettleForward();
+    parts |= MixerPool::kCtx;
+    ctx_routes = s.cbank->routes();
+  }
   if (status()) return status();
   ls_predicted_ = false;
   ever_ran_ = true;
-  return pool_->JoinLockstep(slot_, parts, lstm_slot, mixer_ctx_col, ind_ctx_col, match_cols);
+  return pool_->JoinLockstep(slot_, parts, lstm_slot, mixer_ctx_col, ind_ctx_col, match_cols, ctx_routes);
 }
 
 inline void GpuMixerBank::FinishLockstep() {
@@ -2341,6 +3047,7 @@ inline int GpuMixerBank::EndLockstep() {
 }
 
 inline int GpuMixerBank::SlotsHome() {
+  if (GpuCtxBank* cb = st().cbank) cb->HomeFromDevice();  // the context objects' ShortTermMemory fields
   if (GpuMatchBank* mb = st().match) mb->HomeFromDevice(stm_, sink_ && sink_->SilentSlotsAreZero());
   GpuIndirectBank* ib = st().indirect;
   if (!ib) return status();
@@ -2369,6 +3076,10 @@ inline int GpuMixerBank::Flush() {
     if (track_seen_ && v.match_longest)  // the rows of the mixers whose gate context is longest_match
       for (uint64_t i = 0; i < v.n; ++i)
         for (int32_t j : match_cols_) MarkSeen((size_t)j, v.match_longest[i]);
+    if (track_seen_ && v.ctx_values)  // ... and of those whose gate context is a context object on the device
+      for (size_t j = 0; j < ctx_obj_col_.size(); ++j)
+        if (ctx_obj_col_[j] >= 0)
+          for (uint64_t i = 0; i < v.n; ++i) MarkSeen(j, v.ctx_values[i * (size_t)v.n_ctx_vars + ctx_obj_col_[j]]);
     if (v.ind_active) last_ind_active_.assign(v.ind_active + (v.n - 1) * 2 * (size_t)v.n_ind, v.ind_active + v.n * 2 * (size_t)v.n_ind);
     if (st().lstm) {
       st().lstm->range_on_device_ = true;
@@ -2400,7 +3111,8 @@ inline void GpuMixerBank::PredictAll(ShortTermMemory& stm) {
     for (int w = 0; w < pool_->mask_words_; ++w) m[w] = 0;
     for (int idx : stm.active_models) m[idx >> 5] |= 1u << (idx & 31);
     uint32_t* c = gmx_chainstep_contexts(cs) + (size_t)slot_ * mixers_.size();
-    for (size_t j = 0; j < mixers_.size(); ++j) c[j] = mixers_[j]->context();
+    for (size_t j = 0; j < mixers_.size(); ++j)
+      if (!s.croutes || s.croutes->mixers[j] < 0) c[j] = mixers_[j]->context();
     pool_->ls_what_[slot_] |= GMX_STEP_PREDICT;
     ls_predicted_ = true;
     ever_ran_ = true;
@@ -2425,7 +3137,8 @@ inline void GpuMixerBank::PredictAll(ShortTermMemory& stm) {
     for (int w = 0; w < mask_words_; ++w) m[w] = 0;
     for (int idx : stm.active_models) m[idx >> 5] |= 1u << (idx & 31);
     uint32_t* c = s.ctx + (size_t)s.t * mixers_.size();
-    for (size_t j = 0; j < mixers_.size(); ++j) c[j] = mixers_[j]->context();
+    for (size_t j = 0; j < mixers_.size(); ++j)
+      if (!s.croutes || s.croutes->mixers[j] < 0) c[j] = mixers_[j]->context();
     recorded_ = true;
     return;
   }

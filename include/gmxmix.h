@@ -691,7 +691,8 @@ int gmx_lstm_set_cu_mask(gmx_lstm* l, const uint32_t* mask, int n_words);
  * bit -- into a debugging array of the bank's own batch and into the context columns of up to three record batches
  * of the other banks.  In the lock-step chain the bank steps a bit at a time (gmx_chainstep_attach_ctx below), and so it
  * does on the per-bit surface (gmx_ctx_forward / gmx_ctx_learn) and in the per-bit session chain
- * (gmx_indirect_attach_ctx / gmx_chain_forward_ctx).  The adapter (dropin/) does not use these banks yet. */
+ * (gmx_indirect_attach_ctx / gmx_chain_forward_ctx).  The adapter uses them in the opt-in *_dev builds (dropin/Makefile:
+ * gmx::GpuCtxBank): every surface but the session chain. */
 typedef enum gmx_ctx_kind {
   GMX_CTX_ZERO = 0,             /* always_zero */
   GMX_CTX_BIT_CONTEXT = 1,      /* bit_context = recent_bits - 1 */
