@@ -24,6 +24,7 @@
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
 #include "gmx_ckpt.h"
+#include "gmx_ckpt_stage.h"
 #include "gmx_ind_ckpt.h"
 #include "gmx_match.h"
 #include "gmx_match_ckpt.h"

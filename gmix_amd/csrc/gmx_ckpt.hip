@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "gmx_ckpt.h"
+#include "gmx_ckpt_walk.h"
 
 static_assert(GMX_CKPT_CHUNK == 256, "one thread per row of a chunk, four waves per block");
 
@@ -37,17 +38,8 @@ __device__ __forceinline__ GmxCkptWalk gmx_ckpt_walk(const uint8_t* bank, const 
   if (w.row < x.table_size) w.steps = *GMX_RS_PTR(bank, x, w.row);
   w.live = w.steps != 0;
   const unsigned long long b = __ballot(w.live);
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (lane == 0) wsum[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  uint32_t before = 0, total = 0;
-  for (unsigned k = 0; k < 4; ++k) {
-    const uint32_t c = wsum[k];
-    if (k < wave) before += c;
-    total += c;
-  }
-  w.rank = before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-  w.total = total;
+  w.rank = gmx_walk_rank_step(wsum, (uint32_t)__popcll(b), 0u, &w.total) +
+           (uint32_t)__popcll(b & ((1ull << (threadIdx.x & 63u)) - 1ull));
   return w;
 }
 

@@ -7,17 +7,8 @@
 // Import: the host validates every 12-byte record head of every section first; then the banks are zeroed on the
 // device and the scatter kernel puts the records back.
 //
-// Staging.  The packed bytes pass through ONE device buffer and two pinned host buffers (used in turn, so the host's
-// copy to or from the caller's memory runs beside the device's work on the next slice).  A group may fill most of
-// HBM, so the device buffer does not grow with the group: the streams are processed in slices of consecutive
-// streams whose sections fit kCkptStageBytes together (64 MiB: five streams of the reference's topology after
-// 100 KB of text each, and large enough that a slice's transfer runs at the link's rate).  A slice is never less
-// than one stream, so the buffer's upper bound is the larger of the cap and one stream's section (at most a few
-// bytes per row more than one bank).  GMX_CKPT_STAGE_BYTES in the environment, read at every call, replaces the
-// cap (tests: a few bytes make every stream a slice of its own).
-
-static const size_t kCkptStageBytes = 64u << 20;
-static const int kCkptMaxSliceStreams = 32768;  // grid y / z of the kernels
+// Staging: gmx_ckpt_stage.h -- slices of consecutive streams through one device buffer and two pinned host buffers.
+// Here are its allocations and its link to the device, which the Indirect and the context group checkpoints use too.
 
 extern "C" {
 hipError_t gmx_launch_ckpt_count(const GmxCkptArgs* a, hipStream_t stream);
@@ -33,19 +24,23 @@ struct GmxCkptState {
   uint64_t* off_dev = nullptr;           // export: [streams][chunks]; import: [streams][m]
   uint32_t* mcnt_dev = nullptr;          // [streams][m]
   uint32_t* short_dev = nullptr;         // [streams][6 m]
-  uint8_t* long_dev = nullptr;           // one slice's packed bytes
-  uint8_t* long_host[2] = {nullptr, nullptr};  // pinned
-  size_t cnt_cap = 0, off_cap = 0, mcnt_cap = 0, short_cap = 0, long_cap = 0, long_host_cap[2] = {0, 0};  // bytes
+  CkptStaging stage;                     // one slice's packed bytes
+  size_t cnt_cap = 0, off_cap = 0, mcnt_cap = 0, short_cap = 0;  // bytes
 };
+
+static void ckpt_stage_free(CkptStaging& st) {
+  if (st.dev) (void)hipFree(st.dev);
+  for (uint8_t* p : st.host)
+    if (p) (void)hipHostFree(p);
+}
 
 static void ckpt_free(gmx_group* g) {
   GmxCkptState* c = g->ckpt;
   if (!c) return;
-  void* dev[] = {c->chunks_dev, c->cnt_dev, c->off_dev, c->mcnt_dev, c->short_dev, c->long_dev};
+  void* dev[] = {c->chunks_dev, c->cnt_dev, c->off_dev, c->mcnt_dev, c->short_dev};
   for (void* p : dev)
     if (p) (void)hipFree(p);
-  for (uint8_t* p : c->long_host)
-    if (p) (void)hipHostFree(p);
+  ckpt_stage_free(c->stage);
   delete c;
   g->ckpt = nullptr;
 }
@@ -102,25 +97,32 @@ static int ckpt_state(gmx_group* g, GmxCkptState** out) {
   return GMX_OK;
 }
 
-static size_t ckpt_stage_cap() {
-  const char* e = getenv("GMX_CKPT_STAGE_BYTES");
-  if (e && *e) {
-    const unsigned long long v = strtoull(e, nullptr, 10);
-    if (v > 0) return (size_t)v;
-  }
-  return kCkptStageBytes;
+static int ckpt_stage_grow(CkptStaging& st, const CkptPlan& p) {
+  return st.grow(p.max_slice, p.slices(), ckpt_grow_dev<uint8_t>, ckpt_grow_host);
 }
 
-// Slices of consecutive streams whose sections fit `cap` together; a slice is never less than one stream.
-static void ckpt_slices(const size_t* long_off, int count, size_t cap, std::vector<int>& bounds) {
-  bounds.assign(1, 0);
-  for (int i0 = 0; i0 < count;) {
-    int i1 = i0 + 1;
-    while (i1 < count && i1 - i0 < kCkptMaxSliceStreams && long_off[i1 + 1] - long_off[i0] <= cap) ++i1;
-    bounds.push_back(i1);
-    i0 = i1;
+// The link of gmx_ckpt_stage.h's pipelines: a bank's stream and its staging device buffer.  `ops` (nullable) counts
+// the waits and the transfers, as the callers count their launches.
+struct CkptHipLink {
+  hipStream_t stream;
+  uint8_t* dev;
+  int* ops;
+  int wait() {
+    if (ops) ++*ops;
+    HIPCHK(hipStreamSynchronize(stream));
+    return GMX_OK;
   }
-}
+  int to_host(uint8_t* h, size_t bytes) {
+    if (ops) ++*ops;
+    HIPCHK(hipMemcpyAsync(h, dev, bytes, hipMemcpyDeviceToHost, stream));
+    return GMX_OK;
+  }
+  int to_device(uint8_t* h, size_t bytes) {
+    if (ops) ++*ops;
+    HIPCHK(hipMemcpyAsync(dev, h, bytes, hipMemcpyHostToDevice, stream));
+    return GMX_OK;
+  }
+};
 
 extern "C" int gmx_group_export(gmx_group* g, int first, int count, void* long_buf, size_t long_cap,
                                 size_t* long_off, void* short_buf) {
@@ -180,45 +182,30 @@ extern "C" int gmx_group_export(gmx_group* g, int first, int count, void* long_b
   if (!long_buf) return GMX_OK;  // sizing only
   if (long_cap < long_off[count]) return GMX_ERR_INVALID;
   // ---- pack, slice by slice
-  std::vector<int> sl;
-  ckpt_slices(long_off, count, ckpt_stage_cap(), sl);
-  size_t max_slice = 0;
-  for (size_t k = 0; k + 1 < sl.size(); ++k) {
-    const size_t base = long_off[sl[k]];
-    max_slice = std::max(max_slice, long_off[sl[k + 1]] - base);
-    for (int i = sl[k]; i < sl[k + 1]; ++i)  // offsets inside the slice's buffer
-      for (size_t q = 0; q < K; ++q) coff[(size_t)i * K + q] += long_off[i] - base;
-  }
+  CkptPlan plan;
+  if (!ckpt_plan(long_off, count, ckpt_stage_cap(), plan)) return GMX_ERR_NOMEM;
+  for (int i = 0; i < count; ++i)  // offsets inside the slice's buffer
+    for (size_t q = 0; q < K; ++q) coff[(size_t)i * K + q] += plan.shift[i];
   if ((rc = ckpt_grow_dev(c->off_dev, c->off_cap, coff.size() * sizeof(uint64_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->mcnt_dev, c->mcnt_cap, mcnt.size() * sizeof(uint32_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->short_dev, c->short_cap, (size_t)count * 24 * m))) return rc;
-  if ((rc = ckpt_grow_dev(c->long_dev, c->long_cap, max_slice))) return rc;
-  const int n_host = sl.size() > 2 ? 2 : 1;
-  for (int h = 0; h < n_host; ++h)
-    if ((rc = ckpt_grow_host(c->long_host[h], c->long_host_cap[h], max_slice))) return rc;
+  if ((rc = ckpt_stage_grow(c->stage, plan))) return rc;
   HIPCHK(hipMemcpyAsync(c->off_dev, coff.data(), coff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
   HIPCHK(hipMemcpyAsync(c->mcnt_dev, mcnt.data(), mcnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, g->stream));
   HIPCHK(hipStreamSynchronize(g->stream));  // (pageable sources: gone when this function returns)
-  a.long_buf = (uint32_t*)c->long_dev;
-  auto launch = [&](size_t k) -> int {
-    const int i0 = sl[k];
+  a.long_buf = (uint32_t*)c->stage.dev;
+  CkptHipLink link{g->stream, c->stage.dev, nullptr};
+  rc = ckpt_export_slices(link, plan, long_off, long_buf, c->stage, [&](size_t, int i0, int n) -> int {
     a.banks = g->banks + (size_t)(first + i0) * t.bank_bytes;
-    a.n_streams = sl[k + 1] - i0;
+    a.n_streams = n;
     a.chunk_cnt = c->cnt_dev + (size_t)i0 * K;
     a.chunk_off = c->off_dev + (size_t)i0 * K;
     a.mixer_cnt = c->mcnt_dev + (size_t)i0 * m;
     a.short_buf = c->short_dev + (size_t)i0 * 6 * m;
     HIPCHK(gmx_launch_ckpt_pack(&a, g->stream));
-    HIPCHK(hipMemcpyAsync(c->long_host[k % n_host], c->long_dev, long_off[sl[k + 1]] - long_off[i0],
-                          hipMemcpyDeviceToHost, g->stream));
     return GMX_OK;
-  };
-  if ((rc = launch(0))) return rc;
-  for (size_t k = 0; k + 1 < sl.size(); ++k) {
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (k + 2 < sl.size() && (rc = launch(k + 1))) return rc;  // the next slice packs while this one is copied out
-    memcpy((uint8_t*)long_buf + long_off[sl[k]], c->long_host[k % n_host], long_off[sl[k + 1]] - long_off[sl[k]]);
-  }
+  });
+  if (rc) return rc;
   HIPCHK(hipMemcpy(short_buf, c->short_dev, (size_t)count * 24 * m, hipMemcpyDeviceToHost));
   return GMX_OK;
 }
@@ -285,15 +272,10 @@ extern "C" int gmx_group_import(gmx_group* g, int first, int count, const void* 
                             (const uint8_t*)short_buf + (size_t)i * 24 * m, &mcnt[(size_t)i * m], &moff[(size_t)i * m]);
     if (rcv) return rcv;
   }
-  std::vector<int> sl;
-  ckpt_slices(long_off, count, ckpt_stage_cap(), sl);
-  size_t max_slice = 0;
-  for (size_t k = 0; k + 1 < sl.size(); ++k) {
-    const size_t base = long_off[sl[k]];
-    max_slice = std::max(max_slice, long_off[sl[k + 1]] - base);
-    for (int i = sl[k]; i < sl[k + 1]; ++i)
-      for (size_t j = 0; j < m; ++j) moff[(size_t)i * m + j] += long_off[i] - base;
-  }
+  CkptPlan plan;
+  if (!ckpt_plan(long_off, count, ckpt_stage_cap(), plan)) return GMX_ERR_NOMEM;
+  for (int i = 0; i < count; ++i)
+    for (size_t j = 0; j < m; ++j) moff[(size_t)i * m + j] += plan.shift[i];
   HIPCHK(hipSetDevice(g->device));
   int rc = sessions_close(g, true);
   if (rc) return rc;
@@ -302,10 +284,7 @@ extern "C" int gmx_group_import(gmx_group* g, int first, int count, const void* 
   if ((rc = ckpt_grow_dev(c->off_dev, c->off_cap, moff.size() * sizeof(uint64_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->mcnt_dev, c->mcnt_cap, mcnt.size() * sizeof(uint32_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->short_dev, c->short_cap, (size_t)count * 24 * m))) return rc;
-  if ((rc = ckpt_grow_dev(c->long_dev, c->long_cap, max_slice))) return rc;
-  const int n_host = sl.size() > 2 ? 2 : 1;
-  for (int h = 0; h < n_host; ++h)
-    if ((rc = ckpt_grow_host(c->long_host[h], c->long_host_cap[h], max_slice))) return rc;
+  if ((rc = ckpt_stage_grow(c->stage, plan))) return rc;
   // ---- from here the banks change
   for (int i = 0; i < count; ++i) {
     const int s = first + i;
@@ -321,15 +300,9 @@ extern "C" int gmx_group_import(gmx_group* g, int first, int count, const void* 
   GmxCkptArgs a;
   memset(&a, 0, sizeof a);
   a.topo = g->topo_dev;
-  a.long_buf = (uint32_t*)c->long_dev;
-  for (size_t k = 0; k + 1 < sl.size(); ++k) {
-    const int i0 = sl[k], n = sl[k + 1] - i0;
-    const size_t bytes = long_off[sl[k + 1]] - long_off[i0];
-    uint8_t* const h = c->long_host[k % n_host];
-    // (the upload that last read `h` is two slices back: the wait below, one slice back, was behind it)
-    memcpy(h, (const uint8_t*)long_buf + long_off[i0], bytes);  // beside the device's work on the slice before
-    HIPCHK(hipStreamSynchronize(g->stream));                    // long_dev is free again
-    HIPCHK(hipMemcpyAsync(c->long_dev, h, bytes, hipMemcpyHostToDevice, g->stream));
+  a.long_buf = (uint32_t*)c->stage.dev;
+  CkptHipLink link{g->stream, c->stage.dev, nullptr};
+  return ckpt_import_slices(link, plan, long_off, long_buf, c->stage, [&](size_t, int i0, int n) -> int {
     uint32_t most = 0;
     for (size_t q = 0; q < (size_t)n * m; ++q) most = std::max(most, mcnt[(size_t)i0 * m + q]);
     a.banks = g->banks + (size_t)(first + i0) * t.bank_bytes;
@@ -338,7 +311,6 @@ extern "C" int gmx_group_import(gmx_group* g, int first, int count, const void* 
     a.mixer_off = c->off_dev + (size_t)i0 * m;
     a.short_buf = c->short_dev + (size_t)i0 * 6 * m;
     HIPCHK(gmx_launch_ckpt_scatter(&a, t.m, std::min(std::max((most + 3u) / 4u, 1u), 1024u), g->stream));
-  }
-  HIPCHK(hipStreamSynchronize(g->stream));
-  return GMX_OK;
+    return GMX_OK;
+  });
 }

@@ -23,6 +23,7 @@
 // B[j - k].  The very first Predict of a stream (first_prediction_) opens slot 0 with nothing completed.
 #include <hip/hip_runtime.h>
 
+#include "gmx_ckpt_walk.h"
 #include "gmx_ctx.h"
 #include "gmx_ctx_step.h"
 
@@ -297,48 +298,27 @@ __global__ void gmx_ctx_init_kernel(const GmxCtxDev* __restrict__ dv, uint8_t* b
 __global__ __launch_bounds__(256) void gmx_ctx_ckpt_count_kernel(GmxCtxCkptArgs a) {
   const GmxCtxCkptChunk ch = a.chunks[blockIdx.x];
   const GmxCtxHashDev hd = a.dev->hash[ch.hash];
-  const uint32_t* tab = (const uint32_t*)(a.bank + hd.tab_off);
-  const uint64_t end = min((uint64_t)hd.table_size, (uint64_t)ch.first_entry + GMX_CTX_CKPT_CHUNK);
-  __shared__ uint32_t total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  uint32_t mine = 0;
-  for (uint64_t e = (uint64_t)ch.first_entry + threadIdx.x; e < end; e += 256) mine += tab[e] != 0u;
-  if (mine) atomicAdd(&total, mine);
-  __syncthreads();
+  const uint32_t* tab = (const uint32_t*)(a.bank + hd.tab_off) + ch.first_entry;
+  __shared__ uint32_t wsum[4];
+  const uint32_t end = gmx_walk_chunk_end(hd.table_size, ch.first_entry, GMX_CTX_CKPT_CHUNK);
+  const uint32_t total = gmx_walk_block_count_u32(tab, end, wsum);
   if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = total;
 }
 
-// {key, value} pairs of a sparse table in ascending key order: 256 entries a round, placed by ballot
+// {key, value} pairs of a sparse table in ascending key order, ranked by the walk of gmx_ckpt_walk.h
 __global__ __launch_bounds__(256) void gmx_ctx_ckpt_pack_kernel(GmxCtxCkptArgs a) {
   const GmxCtxCkptChunk ch = a.chunks[blockIdx.x];
   if (a.hash_dense[ch.hash]) return;  // (block-uniform; a dense table is copied as it lies)
   const GmxCtxHashDev hd = a.dev->hash[ch.hash];
-  const uint32_t* tab = (const uint32_t*)(a.bank + hd.tab_off);
-  const uint64_t end = min((uint64_t)hd.table_size, (uint64_t)ch.first_entry + GMX_CTX_CKPT_CHUNK);
-  uint32_t* out = a.buf + a.hash_off[ch.hash];
-  __shared__ uint32_t wcnt[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t base = a.chunk_base[blockIdx.x];
-  for (uint64_t e0 = ch.first_entry; e0 < end; e0 += 256) {
-    const uint64_t e = e0 + threadIdx.x;
-    const uint32_t v = e < end ? tab[e] : 0u;
-    const unsigned long long m = __ballot(v != 0u);
-    if (lane == 0) wcnt[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = base, all = 0;
-    for (int i = 0; i < 4; ++i) {
-      if (i < w) off += wcnt[i];
-      all += wcnt[i];
-    }
-    off += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (v) {
-      out[2 * (size_t)off] = (uint32_t)e;
-      out[2 * (size_t)off + 1] = v;
-    }
-    base += all;
-    __syncthreads();
-  }
+  const uint32_t* tab = (const uint32_t*)(a.bank + hd.tab_off) + ch.first_entry;
+  const uint32_t end = gmx_walk_chunk_end(hd.table_size, ch.first_entry, GMX_CTX_CKPT_CHUNK);
+  uint32_t* const recs = a.buf + a.hash_off[ch.hash] + 2ull * a.chunk_base[blockIdx.x];
+  __shared__ uint32_t wsum[2][4];
+  gmx_walk_pack_sparse_u32(tab, end, ch.first_entry, a.chunk_cnt[blockIdx.x], wsum,
+                           [recs](uint32_t r, uint32_t key, uint32_t v) {
+                             recs[2ull * r] = key;
+                             recs[2ull * r + 1] = v;
+                           });
 }
 
 // import: the pairs of the sparse tables into tables zeroed before (keys checked on the host)

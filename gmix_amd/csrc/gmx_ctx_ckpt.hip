@@ -1,7 +1,8 @@
 // gmx_ctx_ckpt.hip -- the checkpoint of a whole context group on the device (gfx950): count the non-zero entries of
 // every stream's hash tables, assemble every stream's H IndirectHash::WriteToDisk sections (indirect-hash.cpp:33-54) in
-// one device image laid out as the caller's buffer, put such an image back, and gather / scatter the blackboards.  The
-// per-stream kernels of gmx_ctx.hip are untouched: they are what the tests compare these with.
+// one device image laid out as the caller's buffer, put such an image back, and gather / scatter the blackboards.
+// Count and pack walk the tables with gmx_ckpt_walk.h, as the per-stream kernels of gmx_ctx.hip do: the two are no
+// independent witnesses of each other.
 //
 // A table's section: u32 count of non-zero entries; {u32 key, u32 value} in ascending key order (count < size / 2) or
 // the whole table, 4 bytes an entry; u64 outer_context_, u32 outer_hash_.  Every section length is a multiple of 4
@@ -17,7 +18,7 @@
 //   count          one block per (stream, chunk of 16 Ki entries): 4 entries per lane and iteration in one 16-byte
 //                  load, the lanes' counts summed by ballot + popcount; the block of a stream's chunk 0 also copies the
 //                  bank's 16 hash states into the array that travels to the host with the counts.
-//   pack           the same walk.  Sparse: ranks as in gmx_ctx_ckpt_pack_kernel -- pairs of the table's earlier chunks
+//   pack           the same walk.  Sparse: ranks by gmx_walk_pack_sparse_u32 -- pairs of the table's earlier chunks
 //                  (the host's scan) + of the block's earlier rounds + of the waves below + of the lanes below, so the
 //                  pairs ascend without sorting; a chunk without an entry returns at once.  Dense: the chunk's entries
 //                  as they lie.  A table's first chunk writes the count in front and the 12-byte trailer behind.
@@ -32,6 +33,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gmx_ckpt_walk.h"
 #include "gmx_ctx_ckpt.h"
 
 static_assert(sizeof(GmxCtxHashState) == 16 && sizeof(GmxCtxGckTable) == 16, "host and device agree");
@@ -41,23 +43,6 @@ static_assert(offsetof(GmxCtxGckBoard, rotating_history) % 4 == 0 && offsetof(Gm
               "the ring travels in dwords");
 static_assert(GMX_CTX_CKPT_CHUNK % 1024 == 0, "a chunk is a whole number of 256-lane x 4-entry iterations");
 
-// Entries e0 .. e0 + 3 of a chunk that begins at `tab`; entries at or beyond `end` read as 0.
-__device__ __forceinline__ uint4 gmx_cg_load4(const uint32_t* tab, uint32_t e0, uint32_t end) {
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (e0 < end) {
-    v = *(const uint4*)(tab + e0);
-    if (e0 + 1 >= end) v.y = 0u;
-    if (e0 + 2 >= end) v.z = 0u;
-    if (e0 + 3 >= end) v.w = 0u;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t gmx_cg_chunk_end(uint32_t size, uint32_t first_entry) {
-  const uint32_t left = size - first_entry;
-  return left < (uint32_t)GMX_CTX_CKPT_CHUNK ? left : (uint32_t)GMX_CTX_CKPT_CHUNK;
-}
-
 __global__ void __launch_bounds__(256) gmx_ctx_gck_count_kernel(const GmxCtxGckArgs a) {
   __shared__ uint32_t wsum[4];
   const uint32_t s = blockIdx.x / a.n_chunks, c = blockIdx.x % a.n_chunks;
@@ -65,17 +50,9 @@ __global__ void __launch_bounds__(256) gmx_ctx_gck_count_kernel(const GmxCtxGckA
   const GmxCtxHashDev& x = a.dev->hash[ch.hash];
   const uint8_t* bank = a.banks + (uint64_t)s * a.dev->bank_bytes;
   const uint32_t* tab = (const uint32_t*)(bank + x.tab_off) + ch.first_entry;
-  const uint32_t end = gmx_cg_chunk_end(x.table_size, ch.first_entry);
-  uint32_t n = 0;  // at most 16 iterations x 4 entries
-  for (uint32_t e0 = threadIdx.x * 4u; e0 < end; e0 += 1024u) {
-    const uint4 v = gmx_cg_load4(tab, e0, end);
-    n += (uint32_t)(v.x != 0u) + (uint32_t)(v.y != 0u) + (uint32_t)(v.z != 0u) + (uint32_t)(v.w != 0u);
-  }
-  uint32_t total = 0;  // n <= 64: seven ballots
-  for (uint32_t b = 0; b < 7; ++b) total += (uint32_t)__popcll(__ballot((n >> b) & 1u)) << b;
-  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  const uint32_t end = gmx_walk_chunk_end(x.table_size, ch.first_entry, GMX_CTX_CKPT_CHUNK);
+  const uint32_t total = gmx_walk_block_count_u32(tab, end, wsum);
+  if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = total;
   if (c == 0 && threadIdx.x < GMX_CTX_MAX_HASH * sizeof(GmxCtxHashState) / 4)
     ((uint32_t*)(a.states + (uint64_t)s * GMX_CTX_MAX_HASH))[threadIdx.x] =
         ((const uint32_t*)(bank + a.dev->hstate_off))[threadIdx.x];
@@ -89,7 +66,7 @@ __global__ void __launch_bounds__(256) gmx_ctx_gck_pack_kernel(const GmxCtxGckAr
   const uint8_t* bank = a.banks + (uint64_t)s * a.dev->bank_bytes;
   const uint32_t* tab = (const uint32_t*)(bank + x.tab_off) + ch.first_entry;
   const uint32_t size = x.table_size;
-  const uint32_t end = gmx_cg_chunk_end(size, ch.first_entry);
+  const uint32_t end = gmx_walk_chunk_end(size, ch.first_entry, GMX_CTX_CKPT_CHUNK);
   const GmxCtxGckTable tb = a.tb[(uint64_t)s * (uint32_t)a.dev->h + ch.hash];
   uint32_t* const out = (uint32_t*)(a.image + tb.off);
   if (ch.first_entry == 0 && threadIdx.x < 4u) {  // the count in front of the body, the hash state behind it
@@ -103,7 +80,7 @@ __global__ void __launch_bounds__(256) gmx_ctx_gck_pack_kernel(const GmxCtxGckAr
   if (tb.dense) {
     uint32_t* const body = out + 1 + ch.first_entry;
     for (uint32_t e0 = threadIdx.x * 4u; e0 < end; e0 += 1024u) {
-      const uint4 v = gmx_cg_load4(tab, e0, end);
+      const uint4 v = gmx_walk_load4(tab, e0, end);
       body[e0] = v.x;
       if (e0 + 1 < end) body[e0 + 1] = v.y;
       if (e0 + 2 < end) body[e0 + 2] = v.z;
@@ -111,34 +88,13 @@ __global__ void __launch_bounds__(256) gmx_ctx_gck_pack_kernel(const GmxCtxGckAr
     }
     return;
   }
-  // (the banks do not change between the count pass and this one: should they ever, a chunk still writes no more
-  // pairs than the scan gave it room for)
   const uint32_t room = a.chunk_cnt[blockIdx.x];
   if (room == 0) return;  // (uniform over the block)
   uint32_t* const recs = out + 1 + 2ull * a.chunk_base[blockIdx.x];
-  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  uint32_t done = 0, it = 0;
-  for (uint32_t e0 = 0; e0 < end && done < room; e0 += 256u, ++it) {  // (uniform over the block)
-    const uint32_t e = e0 + threadIdx.x;
-    const uint32_t v = e < end ? tab[e] : 0u;
-    const unsigned long long bal = __ballot(v != 0u);
-    // (two sets of sums in turn: a wave that runs ahead writes the other set, and cannot come back to this one
-    // before every wave has passed the next barrier)
-    if (lane == 0) wsum[it & 1u][wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t r = done + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < 4; ++w) {
-      const uint32_t t = wsum[it & 1u][w];
-      if (w < wave) r += t;
-      all += t;
-    }
-    if (v != 0u && r < room) {
-      recs[2ull * r] = ch.first_entry + e;
-      recs[2ull * r + 1] = v;
-    }
-    done += all;
-  }
+  gmx_walk_pack_sparse_u32(tab, end, ch.first_entry, room, wsum, [recs](uint32_t r, uint32_t key, uint32_t v) {
+    recs[2ull * r] = key;
+    recs[2ull * r + 1] = v;
+  });
 }
 
 // block = (stream, table, slice of a.blocks)
@@ -218,19 +174,12 @@ __global__ void __launch_bounds__(256) gmx_ctx_gck_board_scatter_kernel(const Gm
   if (t < GMX_CTX_RING / 4) ((uint32_t*)bd->ring)[t] = ((const uint32_t*)in->rotating_history)[t];
 }
 
-#define GMX_CTX_GCK_LAUNCH(fn, kernel, grid)                                                   \
-  extern "C" hipError_t fn(const GmxCtxGckArgs* a, hipStream_t stream) {                       \
-    (void)hipGetLastError();                                                                   \
-    const uint64_t blocks_ = (grid);                                                           \
-    if (blocks_ == 0 || blocks_ > 0x7fffffffull) return hipErrorInvalidValue;                  \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks_), dim3(256), 0, stream, *a);             \
-    return hipGetLastError();                                                                  \
-  }
-
-GMX_CTX_GCK_LAUNCH(gmx_launch_ctx_gck_count, gmx_ctx_gck_count_kernel, (uint64_t)a->n_streams * a->n_chunks)
-GMX_CTX_GCK_LAUNCH(gmx_launch_ctx_gck_pack, gmx_ctx_gck_pack_kernel, (uint64_t)a->n_streams * a->n_chunks)
-GMX_CTX_GCK_LAUNCH(gmx_launch_ctx_gck_board_gather, gmx_ctx_gck_board_gather_kernel, (uint64_t)a->n_streams)
-GMX_CTX_GCK_LAUNCH(gmx_launch_ctx_gck_board_scatter, gmx_ctx_gck_board_scatter_kernel, (uint64_t)a->n_streams)
+#define GCK_LAUNCH(name, grid) \
+  GMX_WALK_LAUNCH(gmx_launch_ctx_gck_##name, GmxCtxGckArgs, gmx_ctx_gck_##name##_kernel, grid)
+GCK_LAUNCH(count, (uint64_t)a->n_streams * a->n_chunks)
+GCK_LAUNCH(pack, (uint64_t)a->n_streams * a->n_chunks)
+GCK_LAUNCH(board_gather, (uint64_t)a->n_streams)
+GCK_LAUNCH(board_scatter, (uint64_t)a->n_streams)
 // (n_hash: the host's copy of dev->h)
 #define GMX_CTX_GCK_LAUNCH_H(fn, kernel)                                                       \
   extern "C" hipError_t fn(const GmxCtxGckArgs* a, int n_hash, hipStream_t stream) {           \

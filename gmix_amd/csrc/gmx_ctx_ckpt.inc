@@ -1,11 +1,10 @@
 // gmx_ctx_ckpt.inc -- gmx_ctx_group_export / _import and gmx_ctx_group_blackboard_get / _set: the checkpoint of streams
 // [first, first + count) of a context bank in one call.  Included by gmx_capi.cpp behind gmx_ckpt.inc and gmx_ctx.inc;
-// kernels in gmx_ctx_ckpt.hip.  The per-stream calls of gmx_ctx.inc are untouched (but for ctx_validate_section, which
-// both imports call) and are what the tests compare with.
+// kernels in gmx_ctx_ckpt.hip.  The per-stream calls of gmx_ctx.inc keep their own host code (but for
+// ctx_validate_section, which both imports call); their kernels share the walk of gmx_ckpt_walk.h with these.
 //
-// Staging is gmx_ckpt.inc's: one device buffer and two pinned host buffers used in turn, the streams taken in slices of
-// consecutive streams whose sections fit the cap together (ckpt_slices, ckpt_stage_cap: 64 MiB, or
-// GMX_CKPT_STAGE_BYTES), never less than one stream.  A stock stream's sections approach its 201 MB of tables once
+// Staging is gmx_ckpt_stage.h's, through gmx_ckpt.inc's allocations and link, which counts its waits and transfers
+// in cb->gck_ops as GCK counts the calls made here.  A stock stream's sections approach its 201 MB of tables once
 // they are dense: an image of a whole group would not fit beside the banks.  The buffers grow only and stay with the
 // bank (freed by gmx_ctx_destroy): a bank that is checkpointed every generation allocates at its first checkpoint.
 //
@@ -40,20 +39,18 @@ static_assert(sizeof(GmxCtxGckBoard) == sizeof(gmx_ctx_blackboard) &&
 struct GmxCtxGckState {
   uint8_t* back_dev = nullptr;   // count's results: counts [streams][chunks], hash states [streams][16]
   uint8_t* meta_dev = nullptr;   // the scan's results: tables [streams][h], chunk bases [streams][chunks]
-  uint8_t* img_dev = nullptr;    // one slice's sections
   uint8_t* board_dev = nullptr;  // [streams] gmx_ctx_blackboard
-  uint8_t* img_host[2] = {nullptr, nullptr};  // pinned
-  size_t back_cap = 0, meta_cap = 0, img_cap = 0, board_cap = 0, img_host_cap[2] = {0, 0};  // bytes
+  CkptStaging img;               // one slice's sections
+  size_t back_cap = 0, meta_cap = 0, board_cap = 0;  // bytes
 };
 
 static void ctx_gck_free(gmx_ctx* cb) {
   GmxCtxGckState* c = cb->gck;
   if (!c) return;
-  void* dev[] = {c->back_dev, c->meta_dev, c->img_dev, c->board_dev};
+  void* dev[] = {c->back_dev, c->meta_dev, c->board_dev};
   for (void* p : dev)
     if (p) (void)hipFree(p);
-  for (uint8_t* p : c->img_host)
-    if (p) (void)hipHostFree(p);
+  ckpt_stage_free(c->img);
   delete c;
   cb->gck = nullptr;
 }
@@ -79,17 +76,12 @@ static uint32_t ctx_gck_blocks(uint64_t items) { return (uint32_t)std::min<uint6
 
 extern "C" int gmx_debug_ctx_group_ops(const gmx_ctx* cb) { return cb ? cb->gck_ops : GMX_ERR_INVALID; }
 
-// Slices of the window and the largest slice's bytes; tb[].off becomes an offset inside the table's slice.
-static size_t ctx_gck_slice(const size_t* off, int count, size_t H, GmxCtxGckTable* tb, std::vector<int>& sl) {
-  ckpt_slices(off, count, ckpt_stage_cap(), sl);
-  size_t max_slice = 0;
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    const size_t base = off[sl[s]];
-    max_slice = std::max(max_slice, off[sl[s + 1]] - base);
-    for (int i = sl[s]; i < sl[s + 1]; ++i)
-      for (size_t j = 0; j < H; ++j) tb[(size_t)i * H + j].off += off[i] - base;
-  }
-  return max_slice;
+// The slices of the window; tb[].off becomes an offset inside the table's slice.
+static bool ctx_gck_plan(const size_t* off, int count, size_t H, GmxCtxGckTable* tb, CkptPlan& plan) {
+  if (!ckpt_plan(off, count, ckpt_stage_cap(), plan)) return false;
+  for (int i = 0; i < count; ++i)
+    for (size_t j = 0; j < H; ++j) tb[(size_t)i * H + j].off += plan.shift[i];
+  return true;
 }
 
 extern "C" int gmx_ctx_group_export(gmx_ctx* cb, int first, int count, void* buf, size_t cap, size_t* off,
@@ -117,7 +109,7 @@ extern "C" int gmx_ctx_group_export(gmx_ctx* cb, int first, int count, void* buf
   const size_t cnt_bytes = round_up64(n * C * 4, 16), st_bytes = n * GMX_CTX_MAX_HASH * sizeof(GmxCtxHashState);
   const size_t tb_bytes = n * H * sizeof(GmxCtxGckTable);
   std::vector<uint8_t> back, meta;
-  std::vector<int> sl;
+  CkptPlan plan;
   try {
     back.resize(cnt_bytes + st_bytes);
     meta.assign(tb_bytes + n * C * 4, 0);
@@ -163,33 +155,23 @@ extern "C" int gmx_ctx_group_export(gmx_ctx* cb, int first, int count, void* buf
   if (!buf) return GMX_OK;  // sizing only
   if (cap < off[count]) return GMX_ERR_INVALID;
   // ---- pack, slice by slice
-  const size_t max_slice = ctx_gck_slice(off, count, H, tb, sl);
+  if (!ctx_gck_plan(off, count, H, tb, plan)) return GMX_ERR_NOMEM;
   if ((rc = ckpt_grow_dev(c->meta_dev, c->meta_cap, meta.size()))) return rc;
-  if ((rc = ckpt_grow_dev(c->img_dev, c->img_cap, max_slice))) return rc;
-  const int n_host = sl.size() > 2 ? 2 : 1;
-  for (int h = 0; h < n_host; ++h)
-    if ((rc = ckpt_grow_host(c->img_host[h], c->img_host_cap[h], max_slice))) return rc;
+  if ((rc = ckpt_stage_grow(c->img, plan))) return rc;
   GCK(hipMemcpyAsync(c->meta_dev, meta.data(), meta.size(), hipMemcpyHostToDevice, cb->stream));
-  a.image = c->img_dev;
-  auto launch = [&](size_t s) -> int {
-    const size_t i0 = (size_t)sl[s];
+  a.image = c->img.dev;
+  CkptHipLink link{cb->stream, c->img.dev, &cb->gck_ops};
+  // (`meta` is pageable: read by the first slice's wait)
+  return ckpt_export_slices(link, plan, off, buf, c->img, [&](size_t, int s0, int ns) -> int {
+    const size_t i0 = (size_t)s0;
     a.banks = cb->banks + ((size_t)first + i0) * d.bank_bytes;
-    a.n_streams = (uint32_t)(sl[s + 1] - sl[s]);
+    a.n_streams = (uint32_t)ns;
     a.chunk_cnt = (uint32_t*)c->back_dev + i0 * C;
     a.tb = (const GmxCtxGckTable*)c->meta_dev + i0 * H;
     a.chunk_base = (const uint32_t*)(c->meta_dev + tb_bytes) + i0 * C;
     GCK(gmx_launch_ctx_gck_pack(&a, cb->stream));
-    GCK(hipMemcpyAsync(c->img_host[s % n_host], c->img_dev, off[sl[s + 1]] - off[i0], hipMemcpyDeviceToHost,
-                       cb->stream));
     return GMX_OK;
-  };
-  if ((rc = launch(0))) return rc;
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    GCK(hipStreamSynchronize(cb->stream));  // (slice s lies in its host buffer; `meta` is pageable: read by now)
-    if (s + 2 < sl.size() && (rc = launch(s + 1))) return rc;  // the next slice packs while this one is copied out
-    memcpy((uint8_t*)buf + off[sl[s]], c->img_host[s % n_host], off[sl[s + 1]] - off[sl[s]]);
-  }
-  return GMX_OK;
+  });
 }
 
 extern "C" int gmx_ctx_group_import(gmx_ctx* cb, int first, int count, const void* buf, const size_t* off) {
@@ -203,7 +185,7 @@ extern "C" int gmx_ctx_group_import(gmx_ctx* cb, int first, int count, const voi
   cb->gck_ops = 0;
   // ---- every section is checked before any bank is touched
   std::vector<GmxCtxGckTable> tb;
-  std::vector<int> sl;
+  CkptPlan plan;
   try {
     tb.resize(n * H + 1);
   } catch (const std::bad_alloc&) {
@@ -225,7 +207,7 @@ extern "C" int gmx_ctx_group_import(gmx_ctx* cb, int first, int count, const voi
     }
   }
   if (H == 0) return GMX_OK;
-  const size_t max_slice = ctx_gck_slice(off, count, H, tb.data(), sl);
+  if (!ctx_gck_plan(off, count, H, tb.data(), plan)) return GMX_ERR_NOMEM;
   HIPCHK(hipSetDevice(cb->device));
   {
     int rcs = ctx_settle(cb);
@@ -236,10 +218,7 @@ extern "C" int gmx_ctx_group_import(gmx_ctx* cb, int first, int count, const voi
   if (rc) return rc;
   const size_t tb_bytes = n * H * sizeof(GmxCtxGckTable);
   if ((rc = ckpt_grow_dev(c->meta_dev, c->meta_cap, tb_bytes))) return rc;
-  if ((rc = ckpt_grow_dev(c->img_dev, c->img_cap, max_slice))) return rc;
-  const int n_host = sl.size() > 2 ? 2 : 1;
-  for (int h = 0; h < n_host; ++h)
-    if ((rc = ckpt_grow_host(c->img_host[h], c->img_host_cap[h], max_slice))) return rc;
+  if ((rc = ckpt_stage_grow(c->img, plan))) return rc;
   GCK(hipStreamSynchronize(cb->stream));  // (drains the bank's stream, as gmx_ctx_import does)
   // ---- from here the banks change
   GmxCtxGckArgs a;
@@ -248,25 +227,20 @@ extern "C" int gmx_ctx_group_import(gmx_ctx* cb, int first, int count, const voi
   a.dev = cb->dev_d;
   a.n_streams = (uint32_t)count;
   a.tb = (const GmxCtxGckTable*)c->meta_dev;
-  a.image = c->img_dev;
+  a.image = c->img.dev;
   GCK(hipMemcpyAsync(c->meta_dev, tb.data(), tb_bytes, hipMemcpyHostToDevice, cb->stream));
   a.blocks = ctx_gck_blocks(room / 4);  // 16 bytes a lane
   GCK(gmx_launch_ctx_gck_zero(&a, d.h, cb->stream));
   a.blocks = ctx_gck_blocks(most);
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    const size_t i0 = (size_t)sl[s], bytes = off[sl[s + 1]] - off[i0];
-    uint8_t* const h = c->img_host[s % n_host];
-    // (the upload that last read `h` is two slices back: the wait below, one slice back, was behind it)
-    memcpy(h, lb + off[i0], bytes);            // beside the device's work on the slice before
-    GCK(hipStreamSynchronize(cb->stream));     // img_dev is free again (and `tb` is pageable: read by now)
-    GCK(hipMemcpyAsync(c->img_dev, h, bytes, hipMemcpyHostToDevice, cb->stream));
-    a.banks = cb->banks + ((size_t)first + i0) * d.bank_bytes;
-    a.n_streams = (uint32_t)(sl[s + 1] - sl[s]);
-    a.tb = (const GmxCtxGckTable*)c->meta_dev + i0 * H;
+  CkptHipLink link{cb->stream, c->img.dev, &cb->gck_ops};
+  // (`tb` is pageable: read by the first slice's wait)
+  return ckpt_import_slices(link, plan, off, lb, c->img, [&](size_t, int s0, int ns) -> int {
+    a.banks = cb->banks + ((size_t)first + (size_t)s0) * d.bank_bytes;
+    a.n_streams = (uint32_t)ns;
+    a.tb = (const GmxCtxGckTable*)c->meta_dev + (size_t)s0 * H;
     GCK(gmx_launch_ctx_gck_scatter(&a, d.h, cb->stream));
-  }
-  GCK(hipStreamSynchronize(cb->stream));
-  return GMX_OK;
+    return GMX_OK;
+  });
 }
 
 // ---- the blackboards -------------------------------------------------------------------------------

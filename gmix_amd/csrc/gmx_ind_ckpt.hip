@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gmx_ckpt_walk.h"
 #include "gmx_ind_ckpt.h"
 
 static_assert(GMX_IND_CKPT_STEP == 256 * 8, "256 lanes, 8 entries each");
@@ -74,9 +75,6 @@ __device__ __forceinline__ void gmx_ic_put_record(uint8_t* d, uint32_t key, uint
     d[5] = (uint8_t)(entry >> 8);
   }
 }
-__device__ __forceinline__ uint32_t gmx_ic_get_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
 
 // ---- the walk -------------------------------------------------------------------------------------------------------
 // Entries e0 .. e0 + 7 of a chunk (one 16-byte granule; a table's room in the bank is a multiple of 256 bytes, so the
@@ -105,20 +103,6 @@ __device__ __forceinline__ GmxIcGranule gmx_ic_load(const uint8_t* tab, uint32_t
   return g;
 }
 
-// Sum of `v` (below 2^bits) over the wave, and over the lanes below this one: ballot + popcount per bit of v.
-__device__ __forceinline__ void gmx_ic_wave_sum(uint32_t v, uint32_t bits, uint32_t* below, uint32_t* total) {
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  uint32_t b = 0, t = 0;
-  for (uint32_t k = 0; k < bits; ++k) {
-    const unsigned long long bal = __ballot((v >> k) & 1u);
-    b += (uint32_t)__popcll(bal & lt) << k;
-    t += (uint32_t)__popcll(bal) << k;
-  }
-  *below = b;
-  *total = t;
-}
-
 __global__ void __launch_bounds__(256) gmx_ind_ckpt_count_kernel(const GmxIndCkptArgs a) {
   __shared__ uint32_t wsum[4];
   const uint32_t c = blockIdx.x, s = blockIdx.y;
@@ -129,11 +113,10 @@ __global__ void __launch_bounds__(256) gmx_ind_ckpt_count_kernel(const GmxIndCkp
   uint32_t n = 0;  // at most 8 iterations x 8 entries
   for (uint32_t e0 = threadIdx.x * 8u; e0 < end; e0 += GMX_IND_CKPT_STEP)
     n += (uint32_t)__popc(gmx_ic_load(tab, e0, end).live);
-  uint32_t below, total;
-  gmx_ic_wave_sum(n, 7, &below, &total);
-  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) a.chunk_cnt[(uint64_t)s * a.n_chunks + c] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  uint32_t below, total, all;
+  gmx_walk_wave_sum(n, 7, &below, &total);
+  (void)gmx_walk_rank_step(wsum, total, 0u, &all);
+  if (threadIdx.x == 0) a.chunk_cnt[(uint64_t)s * a.n_chunks + c] = all;
 }
 
 __global__ void __launch_bounds__(256) gmx_ind_ckpt_pack_kernel(const GmxIndCkptArgs a) {
@@ -181,24 +164,13 @@ __global__ void __launch_bounds__(256) gmx_ind_ckpt_pack_kernel(const GmxIndCkpt
   // records than the scan gave it room for)
   const uint32_t room = a.chunk_cnt[(uint64_t)s * a.n_chunks + c];
   uint8_t* rec = out + 4 + 6ull * a.chunk_base[(uint64_t)s * a.n_chunks + c];
-  const unsigned wave = threadIdx.x >> 6;
   uint32_t done = 0, it = 0;
   for (uint32_t i0 = 0; i0 < end; i0 += GMX_IND_CKPT_STEP, ++it) {  // (uniform over the block)
     const uint32_t e0 = i0 + threadIdx.x * 8u;
     const GmxIcGranule g = gmx_ic_load(tab, e0, end);
-    uint32_t below, total;
-    gmx_ic_wave_sum((uint32_t)__popc(g.live), 4, &below, &total);
-    // (two sets of sums in turn: a wave that runs ahead writes the other set, and cannot come back to this one
-    // before every wave has passed the next barrier)
-    if ((threadIdx.x & 63u) == 0) wsum[it & 1u][wave] = total;
-    __syncthreads();
-    uint32_t r = done + below, all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < 4; ++w) {
-      const uint32_t t = wsum[it & 1u][w];
-      if (w < wave) r += t;
-      all += t;
-    }
+    uint32_t below, total, all;
+    gmx_walk_wave_sum((uint32_t)__popc(g.live), 4, &below, &total);
+    uint32_t r = gmx_walk_rank_step(wsum[it & 1u], total, done + below, &all);
 #pragma unroll
     for (uint32_t e = 0; e < 8; ++e)
       if ((g.live >> e) & 1u) {
@@ -226,7 +198,7 @@ __global__ void __launch_bounds__(256) gmx_ind_ckpt_scatter_kernel(const GmxIndC
     body = 6ull * mc;
     for (uint64_t r = first; r < mc; r += stride) {
       const uint8_t* p = in + 6ull * r;
-      const uint32_t key = gmx_ic_get_u32(p);
+      const uint32_t key = gmx_walk_get_u32(p);
       if (key >= size) continue;  // (the host's validation has refused such a section already)
       tab[key] = (uint16_t)((uint32_t)p[4] | ((uint32_t)p[5] << 8));
     }
@@ -238,8 +210,8 @@ __global__ void __launch_bounds__(256) gmx_ind_ckpt_scatter_kernel(const GmxIndC
   if (blockIdx.x == 0) {
     const uint8_t* p = in + body + 8u * threadIdx.x;
     uint32_t* dst = (uint32_t*)(bank + a.dev->pred_off + 2048ull * j) + 2u * threadIdx.x;
-    dst[0] = gmx_ic_get_u32(p);
-    dst[1] = gmx_ic_get_u32(p + 4);
+    dst[0] = gmx_walk_get_u32(p);
+    dst[1] = gmx_walk_get_u32(p + 4);
   }
 }
 

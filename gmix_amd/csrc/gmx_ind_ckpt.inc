@@ -10,9 +10,8 @@
 // ascending); then the banks are reset on the device (the image gmx_indirect_import uploads: every entry 0x00ff,
 // zeros behind the tables) and the scatter kernel puts entries and logits back.
 //
-// Staging is gmx_ckpt.inc's: one device buffer and two pinned host buffers used in turn, the streams taken in slices
-// of consecutive streams whose sections fit the cap together (ckpt_slices, ckpt_stage_cap: 64 MiB, or
-// GMX_CKPT_STAGE_BYTES), never less than one stream.  No second copy of a bank exists on either side of the link.
+// Staging is gmx_ckpt_stage.h's, through gmx_ckpt.inc's allocations and link.  No second copy of a bank exists on
+// either side of the link.
 
 extern "C" {
 hipError_t gmx_launch_ind_ckpt_count(const GmxIndCkptArgs* a, hipStream_t stream);
@@ -28,19 +27,17 @@ struct GmxIndCkptState {
   uint32_t* base_dev = nullptr;          // [streams][chunks]
   uint32_t* mcnt_dev = nullptr;          // [streams][k]
   uint64_t* moff_dev = nullptr;          // [streams][k]
-  uint8_t* buf_dev = nullptr;            // one slice's packed bytes
-  uint8_t* buf_host[2] = {nullptr, nullptr};  // pinned
-  size_t cnt_cap = 0, base_cap = 0, mcnt_cap = 0, moff_cap = 0, buf_cap = 0, buf_host_cap[2] = {0, 0};  // bytes
+  CkptStaging stage;                     // one slice's packed bytes
+  size_t cnt_cap = 0, base_cap = 0, mcnt_cap = 0, moff_cap = 0;  // bytes
 };
 
 static void ind_ckpt_free(gmx_indirect* ib) {
   GmxIndCkptState* c = ib->ckpt;
   if (!c) return;
-  void* dev[] = {c->chunks_dev, c->cnt_dev, c->base_dev, c->mcnt_dev, c->moff_dev, c->buf_dev};
+  void* dev[] = {c->chunks_dev, c->cnt_dev, c->base_dev, c->mcnt_dev, c->moff_dev};
   for (void* p : dev)
     if (p) (void)hipFree(p);
-  for (uint8_t* p : c->buf_host)
-    if (p) (void)hipHostFree(p);
+  ckpt_stage_free(c->stage);
   delete c;
   ib->ckpt = nullptr;
 }
@@ -125,47 +122,30 @@ extern "C" int gmx_indirect_group_export(gmx_indirect* ib, int first, int count,
   if (!buf) return GMX_OK;  // sizing only
   if (cap < off[count]) return GMX_ERR_INVALID;
   // ---- pack, slice by slice
-  std::vector<int> sl;
-  ckpt_slices(off, count, ckpt_stage_cap(), sl);
-  size_t max_slice = 0;
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    const size_t base = off[sl[s]];
-    max_slice = std::max(max_slice, off[sl[s + 1]] - base);
-    for (int i = sl[s]; i < sl[s + 1]; ++i)  // offsets inside the slice's buffer
-      for (size_t j = 0; j < k; ++j) moff[(size_t)i * k + j] += off[i] - base;
-  }
+  CkptPlan plan;
+  if (!ckpt_plan(off, count, ckpt_stage_cap(), plan)) return GMX_ERR_NOMEM;
+  for (int i = 0; i < count; ++i)  // offsets inside the slice's buffer
+    for (size_t j = 0; j < k; ++j) moff[(size_t)i * k + j] += plan.shift[i];
   if ((rc = ckpt_grow_dev(c->base_dev, c->base_cap, cnt.size() * sizeof(uint32_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->mcnt_dev, c->mcnt_cap, mcnt.size() * sizeof(uint32_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->moff_dev, c->moff_cap, moff.size() * sizeof(uint64_t)))) return rc;
-  if ((rc = ckpt_grow_dev(c->buf_dev, c->buf_cap, max_slice))) return rc;
-  const int n_host = sl.size() > 2 ? 2 : 1;
-  for (int h = 0; h < n_host; ++h)
-    if ((rc = ckpt_grow_host(c->buf_host[h], c->buf_host_cap[h], max_slice))) return rc;
+  if ((rc = ckpt_stage_grow(c->stage, plan))) return rc;
   HIPCHK(hipMemcpyAsync(c->base_dev, cnt.data(), cnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ib->stream));
   HIPCHK(hipMemcpyAsync(c->mcnt_dev, mcnt.data(), mcnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ib->stream));
   HIPCHK(hipMemcpyAsync(c->moff_dev, moff.data(), moff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ib->stream));
   HIPCHK(hipStreamSynchronize(ib->stream));  // (pageable sources: gone when this function returns)
-  a.buf = c->buf_dev;
-  auto launch = [&](size_t s) -> int {
-    const int i0 = sl[s];
+  a.buf = c->stage.dev;
+  CkptHipLink link{ib->stream, c->stage.dev, nullptr};
+  return ckpt_export_slices(link, plan, off, buf, c->stage, [&](size_t, int i0, int n) -> int {
     a.banks = ib->banks + (size_t)(first + i0) * d.bank_bytes;
-    a.n_streams = sl[s + 1] - i0;
+    a.n_streams = n;
     a.chunk_cnt = c->cnt_dev + (size_t)i0 * K;
     a.chunk_base = c->base_dev + (size_t)i0 * K;
     a.model_cnt = c->mcnt_dev + (size_t)i0 * k;
     a.model_off = c->moff_dev + (size_t)i0 * k;
     HIPCHK(gmx_launch_ind_ckpt_pack(&a, ib->stream));
-    HIPCHK(hipMemcpyAsync(c->buf_host[s % n_host], c->buf_dev, off[sl[s + 1]] - off[i0], hipMemcpyDeviceToHost,
-                          ib->stream));
     return GMX_OK;
-  };
-  if ((rc = launch(0))) return rc;
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    HIPCHK(hipStreamSynchronize(ib->stream));
-    if (s + 2 < sl.size() && (rc = launch(s + 1))) return rc;  // the next slice packs while this one is copied out
-    memcpy((uint8_t*)buf + off[sl[s]], c->buf_host[s % n_host], off[sl[s + 1]] - off[sl[s]]);
-  }
-  return GMX_OK;
+  });
 }
 
 // gmx_indirect_import's rules over one stream's section, plus: keys of a sparse model strictly ascending.
@@ -222,15 +202,10 @@ extern "C" int gmx_indirect_group_import(gmx_indirect* ib, int first, int count,
                                 &moff[(size_t)i * k]);
     if (rcv) return rcv;
   }
-  std::vector<int> sl;
-  ckpt_slices(off, count, ckpt_stage_cap(), sl);
-  size_t max_slice = 0;
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    const size_t base = off[sl[s]];
-    max_slice = std::max(max_slice, off[sl[s + 1]] - base);
-    for (int i = sl[s]; i < sl[s + 1]; ++i)
-      for (size_t j = 0; j < k; ++j) moff[(size_t)i * k + j] += off[i] - base;
-  }
+  CkptPlan plan;
+  if (!ckpt_plan(off, count, ckpt_stage_cap(), plan)) return GMX_ERR_NOMEM;
+  for (int i = 0; i < count; ++i)
+    for (size_t j = 0; j < k; ++j) moff[(size_t)i * k + j] += plan.shift[i];
   HIPCHK(hipSetDevice(ib->device));
   int rc = ind_sessions_close(ib);
   if (rc) return rc;
@@ -238,10 +213,7 @@ extern "C" int gmx_indirect_group_import(gmx_indirect* ib, int first, int count,
   if ((rc = ind_ckpt_state(ib, &c))) return rc;
   if ((rc = ckpt_grow_dev(c->mcnt_dev, c->mcnt_cap, mcnt.size() * sizeof(uint32_t)))) return rc;
   if ((rc = ckpt_grow_dev(c->moff_dev, c->moff_cap, moff.size() * sizeof(uint64_t)))) return rc;
-  if ((rc = ckpt_grow_dev(c->buf_dev, c->buf_cap, max_slice))) return rc;
-  const int n_host = sl.size() > 2 ? 2 : 1;
-  for (int h = 0; h < n_host; ++h)
-    if ((rc = ckpt_grow_host(c->buf_host[h], c->buf_host_cap[h], max_slice))) return rc;
+  if ((rc = ckpt_stage_grow(c->stage, plan))) return rc;
   HIPCHK(hipStreamSynchronize(ib->stream));
   // ---- from here the banks change
   for (int i = 0; i < count; ++i) {
@@ -256,15 +228,9 @@ extern "C" int gmx_indirect_group_import(gmx_indirect* ib, int first, int count,
   GmxIndCkptArgs a;
   memset(&a, 0, sizeof a);
   a.dev = ib->dev_d;
-  a.buf = c->buf_dev;
-  for (size_t s = 0; s + 1 < sl.size(); ++s) {
-    const int i0 = sl[s], n = sl[s + 1] - i0;
-    const size_t bytes = off[sl[s + 1]] - off[i0];
-    uint8_t* const h = c->buf_host[s % n_host];
-    // (the upload that last read `h` is two slices back: the wait below, one slice back, was behind it)
-    memcpy(h, (const uint8_t*)buf + off[i0], bytes);  // beside the device's work on the slice before
-    HIPCHK(hipStreamSynchronize(ib->stream));         // buf_dev is free again
-    HIPCHK(hipMemcpyAsync(c->buf_dev, h, bytes, hipMemcpyHostToDevice, ib->stream));
+  a.buf = c->stage.dev;
+  CkptHipLink link{ib->stream, c->stage.dev, nullptr};
+  return ckpt_import_slices(link, plan, off, buf, c->stage, [&](size_t, int i0, int n) -> int {
     uint32_t most = 0;  // records, or entries of a dense model, of the slice's largest model
     for (size_t q = 0; q < (size_t)n * k; ++q) {
       const uint32_t m = mcnt[(size_t)i0 * k + q], size = d.m[q % k].size;
@@ -275,7 +241,6 @@ extern "C" int gmx_indirect_group_import(gmx_indirect* ib, int first, int count,
     a.model_cnt = c->mcnt_dev + (size_t)i0 * k;
     a.model_off = c->moff_dev + (size_t)i0 * k;
     HIPCHK(gmx_launch_ind_ckpt_scatter(&a, d.k, std::min(std::max(most / 256u + 1u, 1u), 1024u), ib->stream));
-  }
-  HIPCHK(hipStreamSynchronize(ib->stream));
-  return GMX_OK;
+    return GMX_OK;
+  });
 }

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gmx_ckpt_walk.h"
 #include "gmx_match.h"
 #include "gmx_match_step.h"
 #include "gmx_math.h"
@@ -310,78 +311,38 @@ __global__ void __launch_bounds__(256) gmx_match_ckpt_count_kernel(const GmxMatc
   const GmxMatchCkptChunk ch = a.chunks[blockIdx.x];
   const GmxMatchModelDev& x = a.dev->m[ch.model];
   const uint32_t* tab = (const uint32_t*)(a.bank + x.tab_off) + ch.first_entry;
-  const uint32_t left = x.table_size - ch.first_entry;
-  const uint32_t end = left < (uint32_t)GMX_MATCH_CKPT_CHUNK ? left : (uint32_t)GMX_MATCH_CKPT_CHUNK;
-  uint32_t n = 0;
-  for (uint32_t e = threadIdx.x; e < end; e += 256u) n += tab[e] != 0u;
-  // at most 64 per lane: seven ballots
-  uint32_t total = 0;
-  for (uint32_t b = 0; b < 7; ++b) total += (uint32_t)__popcll(__ballot((n >> b) & 1u)) << b;
-  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  const uint32_t end = gmx_walk_chunk_end(x.table_size, ch.first_entry, GMX_MATCH_CKPT_CHUNK);
+  const uint32_t total = gmx_walk_block_count_u32(tab, end, wsum);
+  if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = total;
 }
 
-// Sparse model: records {u32 key, 5 pointer bytes} in ascending key order -- an entry's rank inside its chunk is
-// the valid entries of the block's earlier iterations + of the waves below + of the lanes below.  Dense model: five
-// bytes per entry.  Records are 9 and 5 bytes long: byte stores, every byte written by exactly one lane.
+// Sparse model: records {u32 key, 5 pointer bytes} in ascending key order, ranked by the walk of gmx_ckpt_walk.h.
+// Dense model: five bytes per entry.  Records are 9 and 5 bytes long: byte stores, every byte written by exactly
+// one lane.
 __global__ void __launch_bounds__(256) gmx_match_ckpt_pack_kernel(const GmxMatchCkptArgs a) {
   __shared__ uint32_t wsum[2][4];
   const uint32_t c = blockIdx.x;
   const GmxMatchCkptChunk ch = a.chunks[c];
   const GmxMatchModelDev& x = a.dev->m[ch.model];
   const uint32_t* tab = (const uint32_t*)(a.bank + x.tab_off) + ch.first_entry;
-  const uint32_t left = x.table_size - ch.first_entry;
-  const uint32_t end = left < (uint32_t)GMX_MATCH_CKPT_CHUNK ? left : (uint32_t)GMX_MATCH_CKPT_CHUNK;
+  const uint32_t end = gmx_walk_chunk_end(x.table_size, ch.first_entry, GMX_MATCH_CKPT_CHUNK);
   uint8_t* const out = a.buf + a.model_off[ch.model];
   if (a.model_dense[ch.model]) {
     for (uint32_t e = threadIdx.x; e < end; e += 256u) {
-      const uint32_t v = tab[e];
       uint8_t* o = out + 5ull * (ch.first_entry + e);
-      o[0] = (uint8_t)v;
-      o[1] = (uint8_t)(v >> 8);
-      o[2] = (uint8_t)(v >> 16);
-      o[3] = (uint8_t)(v >> 24);
+      gmx_walk_put_u32(o, tab[e]);
       o[4] = 0;
     }
     return;
   }
-  const uint32_t room = a.chunk_cnt[c];
   uint8_t* const recs = out + 9ull * a.chunk_base[c];
-  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  uint32_t done = 0, it = 0;
-  for (uint32_t e0 = 0; e0 < end; e0 += 256u, ++it) {  // (uniform over the block)
-    const uint32_t e = e0 + threadIdx.x;
-    const uint32_t v = e < end ? tab[e] : 0u;
-    const unsigned long long bal = __ballot(v != 0u);
-    if (lane == 0) wsum[it & 1u][wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t r = done + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < 4; ++w) {
-      const uint32_t t = wsum[it & 1u][w];
-      if (w < wave) r += t;
-      all += t;
-    }
-    if (v != 0u && r < room) {
-      const uint32_t key = ch.first_entry + e;
-      uint8_t* o = recs + 9ull * r;
-      o[0] = (uint8_t)key;
-      o[1] = (uint8_t)(key >> 8);
-      o[2] = (uint8_t)(key >> 16);
-      o[3] = (uint8_t)(key >> 24);
-      o[4] = (uint8_t)v;
-      o[5] = (uint8_t)(v >> 8);
-      o[6] = (uint8_t)(v >> 16);
-      o[7] = (uint8_t)(v >> 24);
-      o[8] = 0;
-    }
-    done += all;
-  }
-}
-
-__device__ __forceinline__ uint32_t gmx_match_get_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+  const uint32_t room = a.chunk_cnt[c];
+  gmx_walk_pack_sparse_u32(tab, end, ch.first_entry, room, wsum, [recs](uint32_t r, uint32_t key, uint32_t v) {
+    uint8_t* o = recs + 9ull * r;
+    gmx_walk_put_u32(o, key);
+    gmx_walk_put_u32(o + 4, v);
+    o[8] = 0;
+  });
 }
 
 // (the tables have been zeroed; the host has validated the section: keys ascending and below the table size)
@@ -396,11 +357,11 @@ __global__ void __launch_bounds__(256) gmx_match_ckpt_scatter_kernel(const GmxMa
   if (!a.model_dense[j]) {
     for (uint64_t r = first; r < mc; r += stride) {
       const uint8_t* p = in + 9ull * r;
-      const uint32_t key = gmx_match_get_u32(p);
-      if (key < size) tab[key] = gmx_match_get_u32(p + 4);
+      const uint32_t key = gmx_walk_get_u32(p);
+      if (key < size) tab[key] = gmx_walk_get_u32(p + 4);
     }
   } else {
-    for (uint64_t e = first; e < size; e += stride) tab[e] = gmx_match_get_u32(in + 5ull * e);
+    for (uint64_t e = first; e < size; e += stride) tab[e] = gmx_walk_get_u32(in + 5ull * e);
   }
 }
 

@@ -1,7 +1,7 @@
 // gmx_match_ckpt.hip -- the checkpoint of a whole Match group on the device (gfx950): count the valid entries of every
 // stream's tables, assemble every stream's long section (long-term-memory.cpp:70-106) in one device image laid out
-// as the caller's buffer, and put such an image back.  The per-stream kernels of gmx_match.hip are untouched: they
-// are what the tests compare these with.
+// as the caller's buffer, and put such an image back.  Count and pack walk the tables with gmx_ckpt_walk.h, as the
+// per-stream kernels of gmx_match.hip do: the two are no independent witnesses of each other.
 //
 // A stream's long section: u64 history size, the history bytes, then per model u32 count of valid entries (entries
 // that are not 0), the records {u32 key, 5 pointer bytes} in ascending key order (count < 5/9 of the table) or
@@ -23,7 +23,7 @@
 //   count    one block per (stream, chunk of 16 Ki entries): 4 entries per lane and iteration in one 16-byte load, the
 //            lanes' counts summed by ballot + popcount; the block of a stream's chunk 0 also copies the bank's 144
 //            bytes of model and stream states into the array that travels to the host with the counts.
-//   pack     the same walk.  Ranks as in gmx_match_ckpt_pack_kernel: valid entries of the block's earlier iterations
+//   pack     the same walk.  Ranks by gmx_walk_pack_sparse_u32: valid entries of the block's earlier iterations
 //            + of the waves below + of the lanes below, so the records ascend without sorting; a chunk's first record
 //            index comes from the host's scan.  A model's first chunk writes its count and its 2 KiB tail.
 //   history  u64 header and the history bytes [0, hist_size): nothing at or beyond the size is read.
@@ -35,21 +35,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gmx_ckpt_walk.h"
 #include "gmx_match_ckpt.h"
 
 static_assert(sizeof(GmxMatchGckStates) == 144, "8 model states and the stream state, contiguous in a bank");
 static_assert(sizeof(GmxMatchGckModel) == 24 && sizeof(GmxMatchGckStream) == 16, "host and device agree");
 static_assert(GMX_MATCH_CKPT_CHUNK % 1024 == 0, "a chunk is a whole number of 256-lane x 4-entry iterations");
-
-__device__ __forceinline__ void gmx_mk_put_u32(uint8_t* o, uint32_t v) {
-  o[0] = (uint8_t)v;
-  o[1] = (uint8_t)(v >> 8);
-  o[2] = (uint8_t)(v >> 16);
-  o[3] = (uint8_t)(v >> 24);
-}
-__device__ __forceinline__ uint32_t gmx_mk_get_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
 
 // Bytes [0, n) from src to dst, both at any address.  Unit 0 is the `lead` bytes in front of dst's first multiple of
 // 4; unit u >= 1 the four bytes from lead + 4 (u - 1): one dword store at an address that is a multiple of 4 by
@@ -66,23 +57,11 @@ __device__ __forceinline__ void gmx_mk_copy(uint8_t* dst, const uint8_t* src, ui
     }
     const uint64_t at = lead + 4 * (u - 1);
     if (n - at >= 4) {
-      *(uint32_t*)(dst + at) = gmx_mk_get_u32(src + at);
+      *(uint32_t*)(dst + at) = gmx_walk_get_u32(src + at);
     } else {
       for (uint64_t i = at; i < n; ++i) dst[i] = src[i];
     }
   }
-}
-
-// Entries e0 .. e0 + 3 of a chunk that begins at `tab`; entries at or beyond `end` read as 0 (not valid).
-__device__ __forceinline__ uint4 gmx_mk_load4(const uint32_t* tab, uint32_t e0, uint32_t end) {
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (e0 < end) {
-    v = *(const uint4*)(tab + e0);
-    if (e0 + 1 >= end) v.y = 0u;
-    if (e0 + 2 >= end) v.z = 0u;
-    if (e0 + 3 >= end) v.w = 0u;
-  }
-  return v;
 }
 
 __global__ void __launch_bounds__(256) gmx_match_gck_count_kernel(const GmxMatchGckArgs a) {
@@ -92,18 +71,9 @@ __global__ void __launch_bounds__(256) gmx_match_gck_count_kernel(const GmxMatch
   const GmxMatchModelDev& x = a.dev->m[ch.model];
   const uint8_t* bank = a.banks + (uint64_t)s * a.dev->bank_bytes;
   const uint32_t* tab = (const uint32_t*)(bank + x.tab_off) + ch.first_entry;
-  const uint32_t left = x.table_size - ch.first_entry;
-  const uint32_t end = left < (uint32_t)GMX_MATCH_CKPT_CHUNK ? left : (uint32_t)GMX_MATCH_CKPT_CHUNK;
-  uint32_t n = 0;  // at most 16 iterations x 4 entries
-  for (uint32_t e0 = threadIdx.x * 4u; e0 < end; e0 += 1024u) {
-    const uint4 v = gmx_mk_load4(tab, e0, end);
-    n += (uint32_t)(v.x != 0u) + (uint32_t)(v.y != 0u) + (uint32_t)(v.z != 0u) + (uint32_t)(v.w != 0u);
-  }
-  uint32_t total = 0;  // n <= 64: seven ballots
-  for (uint32_t b = 0; b < 7; ++b) total += (uint32_t)__popcll(__ballot((n >> b) & 1u)) << b;
-  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  const uint32_t end = gmx_walk_chunk_end(x.table_size, ch.first_entry, GMX_MATCH_CKPT_CHUNK);
+  const uint32_t total = gmx_walk_block_count_u32(tab, end, wsum);
+  if (threadIdx.x == 0) a.chunk_cnt[blockIdx.x] = total;
   if (c == 0 && threadIdx.x < sizeof(GmxMatchGckStates) / 4)
     ((uint32_t*)(a.states + s))[threadIdx.x] = ((const uint32_t*)(bank + a.dev->mstate_off))[threadIdx.x];
 }
@@ -116,63 +86,41 @@ __global__ void __launch_bounds__(256) gmx_match_gck_pack_kernel(const GmxMatchG
   const uint8_t* bank = a.banks + (uint64_t)s * a.dev->bank_bytes;
   const uint32_t* tab = (const uint32_t*)(bank + x.tab_off) + ch.first_entry;
   const uint32_t size = x.table_size;
-  const uint32_t left = size - ch.first_entry;
-  const uint32_t end = left < (uint32_t)GMX_MATCH_CKPT_CHUNK ? left : (uint32_t)GMX_MATCH_CKPT_CHUNK;
+  const uint32_t end = gmx_walk_chunk_end(size, ch.first_entry, GMX_MATCH_CKPT_CHUNK);
   const GmxMatchGckModel md = a.md[(uint64_t)s * (uint32_t)a.dev->k + ch.model];
   uint8_t* const out = a.image + md.off;
   if (ch.first_entry == 0) {  // the count in front of the model's body, the probabilities and counts behind it
-    if (threadIdx.x == 0) gmx_mk_put_u32(out, md.cnt);
+    if (threadIdx.x == 0) gmx_walk_put_u32(out, md.cnt);
     const uint64_t src = (threadIdx.x < 128u ? a.dev->pred_off : a.dev->cnt_off) + 1024ull * ch.model;
     const uint2 v = ((const uint2*)(bank + src))[threadIdx.x & 127u];
     uint8_t* o = out + 4 + (md.dense ? 5ull * size : 9ull * md.cnt) + 8u * threadIdx.x;
-    gmx_mk_put_u32(o, v.x);
-    gmx_mk_put_u32(o + 4, v.y);
+    gmx_walk_put_u32(o, v.x);
+    gmx_walk_put_u32(o + 4, v.y);
   }
   if (md.dense) {
     uint8_t* const body = out + 4 + 5ull * ch.first_entry;
     for (uint32_t e0 = threadIdx.x * 4u; e0 < end; e0 += 1024u) {
-      const uint4 v = gmx_mk_load4(tab, e0, end);
+      const uint4 v = gmx_walk_load4(tab, e0, end);
       const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (uint32_t i = 0; i < 4; ++i)
         if (e0 + i < end) {
           uint8_t* o = body + 5ull * (e0 + i);
-          gmx_mk_put_u32(o, w[i]);
+          gmx_walk_put_u32(o, w[i]);
           o[4] = 0;
         }
     }
     return;
   }
-  // (the banks do not change between the count pass and this one: should they ever, a chunk still writes no more
-  // records than the scan gave it room for)
   const uint32_t room = a.chunk_cnt[blockIdx.x];
   if (room == 0) return;  // (uniform over the block)
   uint8_t* const recs = out + 4 + 9ull * a.chunk_base[blockIdx.x];
-  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  uint32_t done = 0, it = 0;
-  for (uint32_t e0 = 0; e0 < end && done < room; e0 += 256u, ++it) {  // (uniform over the block)
-    const uint32_t e = e0 + threadIdx.x;
-    const uint32_t v = e < end ? tab[e] : 0u;
-    const unsigned long long bal = __ballot(v != 0u);
-    // (two sets of sums in turn: a wave that runs ahead writes the other set, and cannot come back to this one
-    // before every wave has passed the next barrier)
-    if (lane == 0) wsum[it & 1u][wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t r = done + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < 4; ++w) {
-      const uint32_t t = wsum[it & 1u][w];
-      if (w < wave) r += t;
-      all += t;
-    }
-    if (v != 0u && r < room) {
-      uint8_t* o = recs + 9ull * r;
-      gmx_mk_put_u32(o, ch.first_entry + e);
-      gmx_mk_put_u32(o + 4, v);
-      o[8] = 0;
-    }
-    done += all;
-  }
+  gmx_walk_pack_sparse_u32(tab, end, ch.first_entry, room, wsum, [recs](uint32_t r, uint32_t key, uint32_t v) {
+    uint8_t* o = recs + 9ull * r;
+    gmx_walk_put_u32(o, key);
+    gmx_walk_put_u32(o + 4, v);
+    o[8] = 0;
+  });
 }
 
 // block = (stream, slice of a.blocks)
@@ -217,20 +165,20 @@ __global__ void __launch_bounds__(256) gmx_match_gck_scatter_kernel(const GmxMat
     body = 9ull * md.cnt;
     for (uint64_t r = first; r < md.cnt; r += stride) {
       const uint8_t* p = in + 9ull * r;
-      const uint32_t key = gmx_mk_get_u32(p);
-      if (key < size) tab[key] = gmx_mk_get_u32(p + 4);  // (the host's validation has refused any other section)
+      const uint32_t key = gmx_walk_get_u32(p);
+      if (key < size) tab[key] = gmx_walk_get_u32(p + 4);  // (the host's validation has refused any other section)
     }
   } else {
     body = 5ull * size;
-    for (uint64_t e = first; e < size; e += stride) tab[e] = gmx_mk_get_u32(in + 5ull * e);
+    for (uint64_t e = first; e < size; e += stride) tab[e] = gmx_walk_get_u32(in + 5ull * e);
   }
   if (bx != 0) return;
   {
     const uint8_t* p = in + body + 8u * threadIdx.x;
     const uint64_t dst = (threadIdx.x < 128u ? a.dev->pred_off : a.dev->cnt_off) + 1024ull * j;
     uint32_t* d = (uint32_t*)(bank + dst) + 2u * (threadIdx.x & 127u);
-    d[0] = gmx_mk_get_u32(p);
-    d[1] = gmx_mk_get_u32(p + 4);
+    d[0] = gmx_walk_get_u32(p);
+    d[1] = gmx_walk_get_u32(p + 4);
   }
   if (j != 0) return;
   if (threadIdx.x < k) {
@@ -244,20 +192,13 @@ __global__ void __launch_bounds__(256) gmx_match_gck_scatter_kernel(const GmxMat
   if (threadIdx.x == 64u) ((GmxMatchStreamState*)(bank + a.dev->sstate_off))->hist_size = a.st[s].hist_size;
 }
 
-#define GMX_GCK_LAUNCH(fn, kernel, grid)                                                       \
-  extern "C" hipError_t fn(const GmxMatchGckArgs* a, hipStream_t stream) {                     \
-    (void)hipGetLastError();                                                                   \
-    const uint64_t blocks_ = (grid);                                                           \
-    if (blocks_ == 0 || blocks_ > 0x7fffffffull) return hipErrorInvalidValue;                  \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks_), dim3(256), 0, stream, *a);             \
-    return hipGetLastError();                                                                  \
-  }
-
-GMX_GCK_LAUNCH(gmx_launch_match_gck_count, gmx_match_gck_count_kernel, (uint64_t)a->n_streams * a->n_chunks)
-GMX_GCK_LAUNCH(gmx_launch_match_gck_pack, gmx_match_gck_pack_kernel, (uint64_t)a->n_streams * a->n_chunks)
-GMX_GCK_LAUNCH(gmx_launch_match_gck_history, gmx_match_gck_history_kernel, (uint64_t)a->n_streams * a->blocks)
-GMX_GCK_LAUNCH(gmx_launch_match_gck_restore, gmx_match_gck_restore_kernel, (uint64_t)a->n_streams * a->blocks)
-GMX_GCK_LAUNCH(gmx_launch_match_gck_zero, gmx_match_gck_zero_kernel, (uint64_t)a->n_streams * a->blocks)
+#define GCK_LAUNCH(name, grid) \
+  GMX_WALK_LAUNCH(gmx_launch_match_gck_##name, GmxMatchGckArgs, gmx_match_gck_##name##_kernel, grid)
+GCK_LAUNCH(count, (uint64_t)a->n_streams * a->n_chunks)
+GCK_LAUNCH(pack, (uint64_t)a->n_streams * a->n_chunks)
+GCK_LAUNCH(history, (uint64_t)a->n_streams * a->blocks)
+GCK_LAUNCH(restore, (uint64_t)a->n_streams * a->blocks)
+GCK_LAUNCH(zero, (uint64_t)a->n_streams * a->blocks)
 // (n_models: the host's copy of dev->k)
 extern "C" hipError_t gmx_launch_match_gck_scatter(const GmxMatchGckArgs* a, int n_models, hipStream_t stream) {
   (void)hipGetLastError();

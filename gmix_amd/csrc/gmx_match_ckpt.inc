@@ -1,6 +1,8 @@
 // gmx_match_ckpt.inc -- gmx_match_group_export / gmx_match_group_import: the checkpoint of streams
 // [first, first + count) of a Match bank in one call.  Included by gmx_capi.cpp behind gmx_match.inc; kernels in
-// gmx_match_ckpt.hip.  The per-stream calls of gmx_match.inc are untouched and are what the tests compare with.
+// gmx_match_ckpt.hip.  The per-stream calls of gmx_match.inc keep their own host code; their kernels share the walk
+// of gmx_ckpt_walk.h with these (DESIGN 4.12 names the independent witnesses).  This bank keeps its per-call arena
+// and is no user of gmx_ckpt_stage.h.
 //
 // The number of launches, transfers, synchronisations and allocations of a call does not depend on `count`
 // (mb->gck_ops counts them: gmx_debug_match_group_ops):

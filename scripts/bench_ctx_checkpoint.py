@@ -2,8 +2,9 @@
 """Times the checkpoint of a whole context group: gmx_ctx_group_export / _import and gmx_ctx_group_blackboard_get /
 _set (non-zero entries counted, every section assembled and scattered on the device, gmix_amd/csrc/gmx_ctx_ckpt.hip)
 against a loop of gmx_ctx_export / _import / _blackboard_get / _set over the same streams on the same state, in the
-same process.  The per-stream calls are the code the commit before the group calls had (but for the validation, now a
-function both imports call), so the loop measures that path.
+same process.  The per-stream calls keep the host code (one round trip after the other) that the commit before the
+group calls had, but for the validation, a function both imports call, so the loop measures that path; their count and
+pack kernels walk the tables with gmx_ckpt_walk.h, as the group kernels do.
 
     python scripts/bench_ctx_checkpoint.py --out profiles/ctx_group_checkpoint.json
 

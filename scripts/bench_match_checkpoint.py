@@ -2,7 +2,8 @@
 """Times the checkpoint of a whole Match group: gmx_match_group_export / gmx_match_group_import (valid entries counted,
 every section assembled and scattered on the device, gmix_amd/csrc/gmx_match_ckpt.hip) against a loop of
 gmx_match_export / gmx_match_import over the same streams on the same state, in the same process.  The per-stream
-calls are the code the commit before the group calls had, unchanged, so the loop measures that path.
+calls keep the host code (one round trip after the other) that the commit before the group calls had, so the loop
+measures that path; their count and pack kernels walk the tables with gmx_ckpt_walk.h, as the group kernels do.
 
     python scripts/bench_match_checkpoint.py --out profiles/match_group_checkpoint.json
 
