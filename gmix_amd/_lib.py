@@ -188,6 +188,9 @@ def lib():
     L.gmx_lstm_import.argtypes = [vp, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.gmx_lstm_copy.argtypes = [vp, i32, vp, i32]
     L.gmx_lstm_memory_usage.argtypes = [vp, C.POINTER(u64)]
+    L.gmx_lstm_group_export.argtypes = [vp, i32, i32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_size_t)]
+    L.gmx_lstm_group_import.argtypes = [vp, i32, i32, vp, C.c_size_t, vp, C.c_size_t]
     L.gmx_match_create.argtypes = [C.POINTER(vp), C.POINTER(MatchDesc), i32, u64, i32, i32]
     L.gmx_match_destroy.argtypes = [vp]
     L.gmx_match_destroy.restype = None
@@ -347,3 +350,7 @@ ABI_SYMBOLS = [
     "gmx_debug_ctx_group_ops",
     "gmx_ctx_learn", "gmx_ctx_forward", "gmx_indirect_attach_ctx", "gmx_chain_forward_ctx",
 ]
+
+# What include/gmxmix_lstm_group.h declares on top of that: the extension header's symbols, exported by the same library
+# (ABI_SYMBOLS mirrors include/gmxmix.h alone; its length is pinned by tests/test_chain_ctx_abi.py).
+ABI_SYMBOLS_LSTM_GROUP = ["gmx_lstm_group_export", "gmx_lstm_group_import"]

@@ -20,12 +20,14 @@
 #include <vector>
 
 #include "../../include/gmxmix.h"
+#include "../../include/gmxmix_lstm_group.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
 #include "gmx_ckpt.h"
 #include "gmx_ckpt_stage.h"
 #include "gmx_ind_ckpt.h"
+#include "gmx_lstm_ckpt.h"
 #include "gmx_match.h"
 #include "gmx_match_ckpt.h"
 #include "gmx_ctx.h"
@@ -1520,6 +1522,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 #include "gmx_indirect.inc"
 #include "gmx_ind_ckpt.inc"
 #include "gmx_lstm.inc"
+#include "gmx_lstm_ckpt.inc"
 #include "gmx_match.inc"
 #include "gmx_match_ckpt.inc"
 #include "gmx_ctx.inc"

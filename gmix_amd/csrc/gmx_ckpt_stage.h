@@ -1,7 +1,8 @@
 // gmx_ckpt_stage.h -- the host's staging of a group checkpoint: the one copy that gmx_group_export / _import
-// (gmx_ckpt.inc), gmx_indirect_group_export / _import (gmx_ind_ckpt.inc) and gmx_ctx_group_export / _import
-// (gmx_ctx_ckpt.inc) share.  Nothing here needs HIP: the device and the link to it are the caller's `link`, so that a
-// fake one can play them (tests/cpp/test_ckpt_stage.cpp).
+// (gmx_ckpt.inc), gmx_indirect_group_export / _import (gmx_ind_ckpt.inc), gmx_ctx_group_export / _import
+// (gmx_ctx_ckpt.inc) and gmx_lstm_group_export / _import (gmx_lstm_ckpt.inc: sections of one size, one pass per half)
+// share.  Nothing here needs HIP: the device and the link to it are the caller's `link`, so that a fake one can play
+// them (tests/cpp/test_ckpt_stage.cpp).
 //
 // The packed bytes pass through ONE device buffer and two pinned host buffers (used in turn, so the host's copy to or
 // from the caller's memory runs beside the device's work on the next slice).  A group may fill most of HBM, so the

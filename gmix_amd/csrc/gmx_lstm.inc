@@ -58,7 +58,9 @@ struct gmx_lstm {
   std::vector<struct GmxLstmSession*> sessions;  // per-byte sessions (gmx_lstm_kernel<.., true>), per stream
   bool use_sessions = true;
   bool banks_in_use_by_dead_kernel = false;  // a session block that stopped answering may still hold them: never freed
+  struct GmxLstmCkptState* ckpt = nullptr;  // gmx_lstm_group_export / _import: layout tables and staging (gmx_lstm_ckpt.inc), lazily
 };
+static void lstm_ckpt_free(gmx_lstm* l);
 
 // ---- per-byte sessions: gmx_lstm_forward / gmx_lstm_perceive without a kernel launch per call -----------
 // The protocol and its bounded waits are gmx_mailbox.h, the blocks and the stream of a session GmxSessionHw
@@ -150,6 +152,7 @@ extern "C" void gmx_lstm_destroy(gmx_lstm* l) {
   (void)hipSetDevice(l->device);
   lstm_sessions_free(l);
   if (l->stream) (void)hipStreamSynchronize(l->stream);
+  lstm_ckpt_free(l);
   if (l->one) {
     lstm_batch_free(l->one);
     l->one = nullptr;

@@ -33,6 +33,7 @@
 #include <numeric>
 
 #include "gmx_mixer.h"
+#include "../../include/gmxmix_lstm_group.h"  // gmx::LstmBank::ExportAll / ImportAll
 
 namespace gmx {
 
@@ -538,6 +539,26 @@ class LstmBank {
   }
   void Copy(const LstmBank* orig) {  // long-term-memory.cpp:216-219 + LstmModel::Copy
     if (h_ && orig->h_) Note(gmx_lstm_copy(h_, 0, orig->h_, 0));
+  }
+  // Checkpoint of every stream of this bank's gmx_lstm in one call (gmx_lstm_group_export / gmx_lstm_group_import):
+  // the file layouts are produced on the device.  Stream i's sections -- the bytes WriteToDisk writes for it -- are
+  // long_buf[i * *long_stride ..) and short_buf[i * *short_stride ..).  WriteToDisk / ReadFromDisk above stay on the
+  // per-stream calls (one Predictor's file at a time).
+  int ExportAll(std::vector<char>* long_buf, std::vector<char>* short_buf, size_t* long_stride, size_t* short_stride) {
+    if (!h_) return GMX_ERR_STATE;
+    const int n = gmx_lstm_n_streams(h_);
+    int rc = gmx_lstm_group_export(h_, 0, n, nullptr, 0, nullptr, 0, long_stride, short_stride);
+    if (rc) return rc;
+    long_buf->resize((size_t)n * *long_stride);
+    short_buf->resize((size_t)n * *short_stride);
+    return gmx_lstm_group_export(h_, 0, n, long_buf->data(), long_buf->size(), short_buf->data(), short_buf->size(),
+                                 long_stride, short_stride);
+  }
+  // GMX_ERR_FORMAT, and no bank touched, when any section is malformed.
+  int ImportAll(const std::vector<char>& long_buf, const std::vector<char>& short_buf) {
+    if (!h_) return GMX_ERR_STATE;
+    return gmx_lstm_group_import(h_, 0, gmx_lstm_n_streams(h_), long_buf.data(), long_buf.size(), short_buf.data(),
+                                 short_buf.size());
   }
 
  private:

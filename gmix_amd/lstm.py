@@ -86,6 +86,33 @@ class LstmGroup:
         b = np.frombuffer(short_bytes, np.uint8).copy()
         check(self.L.gmx_lstm_import(self.h, stream, _vp(a), len(a), _vp(b), len(b)), "gmx_lstm_import")
 
+    def export_all(self, first=0, count=None, long=True, short=True):
+        """[(long, short)] of streams [first, first + count) in one call (gmx_lstm_group_export): the sections are laid
+        out on the device; pair i is byte for byte export(first + i).  A half that is not asked for is None."""
+        count = self.S - first if count is None else count
+        nl, ns = C.c_size_t(0), C.c_size_t(0)
+        check(self.L.gmx_lstm_group_export(self.h, first, count, None, 0, None, 0, C.byref(nl), C.byref(ns)),
+              "gmx_lstm_group_export(size)")
+        if count == 0:
+            return []
+        nl, ns = nl.value, ns.value
+        bl = np.zeros(count * nl, np.uint8) if long else None
+        bs = np.zeros(count * ns, np.uint8) if short else None
+        check(self.L.gmx_lstm_group_export(self.h, first, count, _vp(bl), count * nl if long else 0, _vp(bs),
+                                           count * ns if short else 0, None, None), "gmx_lstm_group_export")
+        return [(bl[i * nl:(i + 1) * nl].tobytes() if long else None,
+                 bs[i * ns:(i + 1) * ns].tobytes() if short else None) for i in range(count)]
+
+    def import_all(self, pairs, first=0):
+        """The inverse of export_all (gmx_lstm_group_import): pairs[i] = (long, short) goes to stream first + i.  A
+        malformed section anywhere raises GmxError and leaves every bank as it was."""
+        count = len(pairs)
+        bl = np.frombuffer(b"".join(p[0] for p in pairs) or b"\0", np.uint8)
+        bs = np.frombuffer(b"".join(p[1] for p in pairs) or b"\0", np.uint8)
+        nl = sum(len(p[0]) for p in pairs)
+        ns = sum(len(p[1]) for p in pairs)
+        check(self.L.gmx_lstm_group_import(self.h, first, count, _vp(bl), nl, _vp(bs), ns), "gmx_lstm_group_import")
+
     def copy_from(self, src, src_stream=0, stream=0):
         check(self.L.gmx_lstm_copy(self.h, stream, src.h, src_stream), "gmx_lstm_copy")
 

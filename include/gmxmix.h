@@ -449,6 +449,7 @@ int gmx_lstm_import(gmx_lstm* l, int stream, const void* long_buf, size_t long_b
                     size_t short_bytes);
 int gmx_lstm_copy(gmx_lstm* dst, int dst_stream, gmx_lstm* src, int src_stream);
 int gmx_lstm_memory_usage(gmx_lstm* l, uint64_t* bytes);
+/* Many streams in one call: the group pair of include/gmxmix_lstm_group.h. */
 
 /* ==== Match models ============================================================================
  * The producers of 6 of the mixers' 90 inputs and of the `longest_match` gate context: the reference's `Match`
