@@ -290,6 +290,20 @@ def lib():
         f.restype = vp
     for name in ("gmx_group_set_cu_mask", "gmx_indirect_set_cu_mask", "gmx_lstm_set_cu_mask", "gmx_match_set_cu_mask"):
         getattr(L, name).argtypes = [vp, C.POINTER(u32), i32]
+    if hasattr(L, "gmx_chainstep_attach_decoder"):
+        # (include/gmxmix_decoder.h; an older build loaded through GMX_LIB for a comparison lacks them, and a call fails)
+        L.gmx_chainstep_attach_decoder.argtypes = [vp, i32]
+        L.gmx_chainstep_decoder_set_input.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(u32)]
+        L.gmx_chainstep_decoder_state.argtypes = [vp, i32, C.POINTER(u32)]
+        for name in ("byte", "byte_launch", "byte_wait"):
+            getattr(L, "gmx_chainstep_" + name).argtypes = [vp]
+        L.gmx_chainstep_timed_byte.argtypes = [vp, C.POINTER(C.c_float)]
+        for name in ("decoder_ppm", "take", "decoded", "byte_p"):
+            f = getattr(L, "gmx_chainstep_" + name)
+            f.argtypes = [vp]
+            f.restype = vp
+        L.gmx_debug_chainstep_bit_launches.argtypes = [vp]
+        L.gmx_debug_chainstep_bit_launches.restype = C.c_int64
     L.gmx_debug_math_probe.argtypes = [i32, vp, vp, u64, i32]
     L.gmx_debug_math_range.argtypes = [i32, u64, u64, i32, C.POINTER(C.c_ulonglong)]
     _LIB = L
@@ -354,3 +368,11 @@ ABI_SYMBOLS = [
 # What include/gmxmix_lstm_group.h declares on top of that: the extension header's symbols, exported by the same library
 # (ABI_SYMBOLS mirrors include/gmxmix.h alone; its length is pinned by tests/test_chain_ctx_abi.py).
 ABI_SYMBOLS_LSTM_GROUP = ["gmx_lstm_group_export", "gmx_lstm_group_import"]
+
+# What include/gmxmix_decoder.h declares: a whole byte per call in the lock-step chain.
+ABI_SYMBOLS_DECODER = [
+    "gmx_chainstep_attach_decoder", "gmx_chainstep_decoder_ppm", "gmx_chainstep_decoder_set_input",
+    "gmx_chainstep_decoder_state", "gmx_chainstep_take", "gmx_chainstep_byte", "gmx_chainstep_byte_launch",
+    "gmx_chainstep_byte_wait", "gmx_chainstep_timed_byte", "gmx_chainstep_decoded", "gmx_chainstep_byte_p",
+    "gmx_debug_chainstep_bit_launches",
+]

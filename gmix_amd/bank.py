@@ -433,6 +433,54 @@ class ChainStep:
             setattr(r, "n_" + name + "_route", len(a))
         check(self.L.gmx_chainstep_attach_ctx(self.h, group.h, C.byref(r)), "gmx_chainstep_attach_ctx")
 
+    def attach_decoder(self, ppmd_slot):
+        """The arithmetic decoder and ModPPMD's range walk run on the device from now on
+        (gmx_chainstep_attach_decoder): once, before the first step, after attach_match / attach_ctx.  Afterwards
+        `take` [S], `decoder_ppm` [S][256], `decoded` [S] and `byte_p` [S][8] are views, and byte() decodes a whole byte
+        of every stream with take[s] = 1."""
+        check(self.L.gmx_chainstep_attach_decoder(self.h, int(ppmd_slot)), "gmx_chainstep_attach_decoder")
+        S = self.g.S
+        self.take = self._view("take", np.uint8, (S,))
+        self.decoder_ppm = self._view("decoder_ppm", np.float32, (S, 256))
+        self.decoded = self._view("decoded", np.uint8, (S,))
+        self.byte_p = self._view("byte_p", np.float32, (S, 8))
+
+    def set_input(self, stream, data, state=None):
+        """The stream's compressed payload becomes resident on the device (gmx_chainstep_decoder_set_input).  state
+        None: Decoder's constructor reads the four start bytes; (x1, x2, x, pos): resume, as decoder_state gave it."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        st = (C.c_uint32 * 4)(*[int(v) for v in state]) if state is not None else None
+        check(self.L.gmx_chainstep_decoder_set_input(self.h, stream, buf.ctypes.data if len(buf) else None, len(buf), st),
+              "gmx_chainstep_decoder_set_input")
+
+    def decoder_state(self, stream):
+        """(x1, x2, x, pos) of the stream's decoder after the last answered byte."""
+        out = (C.c_uint32 * 4)()
+        check(self.L.gmx_chainstep_decoder_state(self.h, stream, out), "gmx_chainstep_decoder_state")
+        return tuple(int(v) for v in out)
+
+    def byte(self):
+        """Eight steps in one call for the streams with take[s] = 1 (gmx_chainstep_byte): `decoded` and `byte_p` hold
+        the answers."""
+        check(self.L.gmx_chainstep_byte(self.h), "gmx_chainstep_byte")
+
+    def timed_byte(self):
+        """byte() with HIP events around the byte's graph -> device milliseconds."""
+        ms = C.c_float(0)
+        check(self.L.gmx_chainstep_timed_byte(self.h, C.byref(ms)), "gmx_chainstep_timed_byte")
+        return ms.value
+
+    def byte_launch(self):
+        check(self.L.gmx_chainstep_byte_launch(self.h), "gmx_chainstep_byte_launch")
+
+    def byte_wait(self):
+        check(self.L.gmx_chainstep_byte_wait(self.h), "gmx_chainstep_byte_wait")
+
+    @property
+    def bit_launches(self):
+        """Per-bit graphs launched so far (gmx_debug_chainstep_bit_launches)."""
+        return int(self.L.gmx_debug_chainstep_bit_launches(self.h))
+
     @property
     def commit_bytes(self):
         """Bytes of records per stream a commit moves (gmx_chainstep_commit_bytes)."""

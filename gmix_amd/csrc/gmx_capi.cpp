@@ -21,6 +21,7 @@
 
 #include "../../include/gmxmix.h"
 #include "../../include/gmxmix_lstm_group.h"
+#include "../../include/gmxmix_decoder.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
@@ -32,6 +33,7 @@
 #include "gmx_match_ckpt.h"
 #include "gmx_ctx.h"
 #include "gmx_ctx_ckpt.h"
+#include "gmx_coder_dev.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -1528,6 +1530,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 #include "gmx_ctx.inc"
 #include "gmx_ctx_ckpt.inc"
 #include "gmx_chainstep.inc"
+#include "gmx_coder.inc"
 
 // ---- test probes (device math against host math; not part of the product surface) --------
 extern "C" int gmx_debug_single_variant(gmx_group* g, int lanes_per_stream) {

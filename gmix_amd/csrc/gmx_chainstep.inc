@@ -61,6 +61,39 @@ extern "C" hipError_t gmx_launch_models_step_match(const GmxIndDev* dv, int k_in
                                                    const GmxMatchDev* mdv, const GmxMatchStepArgs* margs, int n_streams,
                                                    hipStream_t stream);
 extern "C" hipError_t gmx_launch_match_step(const GmxMatchDev* dv, const GmxMatchStepArgs* args, hipStream_t stream);
+extern "C" hipError_t gmx_launch_coder_step(const GmxCtxDev* dv, const GmxCoderStepArgs* args, hipStream_t stream);
+extern "C" hipError_t gmx_launch_coder_tail(const GmxCoderStepArgs* args, hipStream_t stream);
+
+// The device arithmetic decoder of a lock-step object (gmx_chainstep_attach_decoder, gmx_coder.inc).
+struct gmx_cs_decoder {
+  int ppmd_slot = -1;
+  GmxCoderStream* streams = nullptr;      // device [S]
+  std::vector<uint8_t*> input;            // device: the streams' compressed payloads
+  GmxCoderByteIn* h_in = nullptr;         // pinned [S]: what the host says per byte ...
+  GmxCoderByteIn* in_dev = nullptr;       // ... where the byte's first step reads it (device memory the host stores into,
+  GmxCoderByteIn* in_bar = nullptr;       //     where there is such a thing: in_bar; else the pinned block itself)
+  float* p_dev = nullptr;                 // device [S]: the mixers' p of the step before
+  float* outs_dev = nullptr;              // device [S][M]: the mixers' outputs of a byte graph's steps (nobody reads them)
+  uint32_t* stamp_dev = nullptr;          // device [S]: ... and their stamps
+  uint8_t* h_ans = nullptr;               // pinned: take [S] | decoded [S] | byte_p [S][8] | state [S][4]
+  uint8_t *take = nullptr, *decoded = nullptr;
+  float* byte_p = nullptr;
+  uint32_t* state = nullptr;
+  uint8_t* ans_dev = nullptr;
+  std::vector<GmxCoderState> st;          // the state after the last answered byte (or as set)
+  std::vector<uint8_t> has_input, via_byte, taking;
+  hipGraph_t graph[2] = {};               // [parity of the byte's first step]
+  hipGraphExec_t exec[2] = {};
+  bool in_flight = false;                 // the step in flight is a byte
+};
+
+// Where a byte graph's steps put what a per-bit step hands to the host, and which step of the byte is recorded.
+struct CsByteRoute {
+  int j;            // 1..8
+  float* p;         // device [S]
+  float* outs;      // device [S][M]
+  uint32_t* stamp;  // device [S]
+};
 
 struct gmx_chainstep {
   gmx_group* g = nullptr;
@@ -124,7 +157,13 @@ struct gmx_chainstep {
   std::vector<uint8_t> nbits;      // bits of the current byte learned so far
   std::vector<uint8_t> acc;        // ... and their value
   uint64_t steps = 0;
+  uint64_t bit_launches = 0;       // per-bit graphs launched so far (gmx_debug_chainstep_bit_launches)
+  gmx_cs_decoder* dc = nullptr;    // gmx_chainstep_attach_decoder
 };
+
+static void cs_decoder_free(gmx_chainstep* cs);
+static void cs_decoder_answered(gmx_chainstep* cs);
+static hipError_t cs_coder_args(gmx_chainstep* cs, int par, int j, GmxCoderStepArgs* ca);
 
 static size_t cs_round(size_t n) { return (n + 255) / 256 * 256; }
 
@@ -173,6 +212,7 @@ extern "C" void gmx_chainstep_destroy(gmx_chainstep* cs) {
     }
   for (hipEvent_t ev : cs->t_ev)
     if (ev) (void)hipEventDestroy(ev);
+  cs_decoder_free(cs);
   void* hv[] = {cs->h_in, cs->h_bd, cs->h_out, cs->adam_host};
   for (void* q : hv)
     if (q) (void)hipHostFree(q);
@@ -182,8 +222,11 @@ extern "C" void gmx_chainstep_destroy(gmx_chainstep* cs) {
   delete cs;
 }
 
-// The step as a stream of work on `st` (captured four times: parity of the step x whether it opens a byte).
-static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int par) {
+// The step as a stream of work on `st` (captured four times: parity of the step x whether it opens a byte).  br
+// (nullable): the step is step br->j of a byte graph (gmx_coder.inc) -- the device writes the step's words and records
+// itself, gmx_coder_step_kernel in place of the context bank's node, so nothing is fetched from the host, and p, the
+// outputs and the stamps stay in device memory.
+static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int par, const CsByteRoute* br = nullptr) {
   gmx_group* g = cs->g;
   const GmxTopoDev& t = g->topo;
   hipError_t e = hipSuccess;
@@ -195,8 +238,14 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
   GmxStepUpload up = cs->up;
   up.src = cs->h_in_dev;
   up.dst = cs->d_in[par];
-  if (cs->bar) up.n = 0;  // the host has put them there
-  if (cs->cb) {
+  if (cs->bar || br) up.n = 0;  // the host has put them there (a byte graph: the step's first kernel writes them)
+  if (br) {
+    GmxCoderStepArgs ca;
+    e = cs_coder_args(cs, par, br->j, &ca);
+    if (e != hipSuccess) return e;
+    e = gmx_launch_coder_step(cs->cb->dev_d, &ca, st);
+    if (e != hipSuccess) return e;
+  } else if (cs->cb) {
     // the context bank's bit: behind the step's words and in front of every consumer of the records it writes.  Where
     // the device fetches the step's inputs the fetch is a node of its own in front of it (inside the models' kernel it
     // would overwrite what this node wrote)
@@ -227,7 +276,7 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
   uint32_t* const ctx_d = (uint32_t*)cur(cs->ctx);
   if (cs->l && opens) {
     gmx_lstm* l = cs->l;
-    if (!cs->bar) {
+    if (!cs->bar && !br) {  // (a byte graph begins with this copy: its first kernel reads the distributions)
       e = gmx_launch_copy16(cs->d_bd, cs->h_bd_dev, cs->bd_bytes / 16, st);
       if (e != hipSuccess) return e;
     }
@@ -365,11 +414,11 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
     sa.pred_new = pred_d;
     sa.mask_new = mask_d;
     sa.ctx_new = ctx_d;
-    sa.p_out = (float*)res(cs->p);
-    sa.out_all = (float*)res(cs->outs);
+    sa.p_out = br ? br->p : (float*)res(cs->p);
+    sa.out_all = br ? br->outs : (float*)res(cs->outs);
     sa.latch = g->latch_out;
     sa.seq = (const uint32_t*)cur(cs->seq);
-    sa.stamp = (uint32_t*)res(cs->stamp);
+    sa.stamp = br ? br->stamp : (uint32_t*)res(cs->stamp);
     sa.n_streams = g->S;
     sa.exact = g->stock_exact ? 1 : 0;
     return gmx_launch_stock_step(g->topo_dev, &sa, GMX_STK_LDS_BYTES(g->topo.lds_misc), st);
@@ -381,8 +430,8 @@ static hipError_t cs_record(gmx_chainstep* cs, hipStream_t st, bool opens, int p
   a.bits = bits_d;
   a.decay = (const float*)cur(cs->dec);
   a.decay_idx = cs->idx_dev;
-  a.p_out = (float*)res(cs->p);
-  a.out_all = (float*)res(cs->outs);
+  a.p_out = br ? br->p : (float*)res(cs->p);
+  a.out_all = br ? br->outs : (float*)res(cs->outs);
   a.latch_out = g->latch_out;
   a.rec_stride = 1;
   a.T = 1;
@@ -932,6 +981,7 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
   const double ta = cs_trace_on() ? cs_now() : 0.0;
   if (cs->timed) HIPCHK(hipEventRecord(cs->t_ev[0], g->stream));
   HIPCHK(hipGraphLaunch(cs->exec[cs->steps & 1][(cs->l && opens) ? 1 : 0], g->stream));
+  cs->bit_launches += 1;
   if (cs->timed) {
     HIPCHK(hipEventRecord(cs->t_ev[1], g->stream));
     cs->timed_ok = true;
@@ -944,7 +994,10 @@ extern "C" int gmx_chainstep_launch(gmx_chainstep* cs) {
       g->steps[s] += 1;
       cs->pending[s] = 0;
     }
-    if (w & GMX_STEP_PREDICT) cs->pending[s] = 1;
+    if (w & GMX_STEP_PREDICT) {
+      cs->pending[s] = 1;
+      if (cs->dc) cs->dc->via_byte[s] = 0;  // (the bit of its Learn is the caller's to give)
+    }
     if (cs->cb && w) cs->cb->outstanding[s] = (w & GMX_STEP_PREDICT) ? 1 : 0;
     if (w) {
       g->fwd_done[s] = 0;
@@ -1007,6 +1060,7 @@ extern "C" int gmx_chainstep_wait(gmx_chainstep* cs) {
     HIPCHK(hipStreamSynchronize(g->stream));
   }
   cs->in_flight = false;
+  if (cs->dc && cs->dc->in_flight) cs_decoder_answered(cs);
   if (cs_trace_on()) {
     g_cs_trace.wait_s += cs_now() - tb;
     if (++g_cs_trace.n % 4096 == 0) {
