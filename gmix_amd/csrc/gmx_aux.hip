@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gmx_coder.h"
 #include "gmx_internal.h"
 #include "gmx_math.h"
 #include "gmx_step_dev.h"
@@ -176,7 +177,8 @@ extern "C" hipError_t gmx_launch_ind_synth_kernel(const GmxIndSynthArgs* args, h
 // ---------------------------------------------------------------------------------------
 // what: 0 expf, 1 logistic, 2 squash-clamp; then what the LSTM byte model calls (gmx_lstm.hip): 5 logf, 6 logit,
 // 7 expm1f, 8 tanhf, 9 the logistic with the 2^(i/32) table in LDS as that kernel holds it, 10 the layer-norm
-// scale of a sum of squares, 11 Adam's step on tuples of six operands.
+// scale of a sum of squares, 11 Adam's step on tuples of six operands; 12 and 13 the byte graphs' two functions
+// (gmx_coder.h) on tuples of 32-bit words carried as floats: the arithmetic decoder's bit, ModPPMD's range walk.
 __device__ __forceinline__ float gmx_math_unary(float v, int what, const uint64_t* lds_tab) {
   switch (what) {
     case 0: return gmx_expf(v);
@@ -191,6 +193,7 @@ __device__ __forceinline__ float gmx_math_unary(float v, int what, const uint64_
   }
 }
 
+#define GMX_PROBE_WALK_SENTINEL 0xc2f60000u  // -123.0f, as tests/cpp/test_coder.cpp presets its slot
 __global__ void gmx_math_probe_kernel(const float* x, float* y, uint64_t n, int what) {
   __shared__ uint64_t tab[32];
   if (threadIdx.x < 32) tab[threadIdx.x] = gmx_exp2f_tab[threadIdx.x];
@@ -201,6 +204,44 @@ __global__ void gmx_math_probe_kernel(const float* x, float* y, uint64_t n, int 
     // x[6j .. 6j+5] = (weight, alpha, m, d1, v, d2) of tuple j, the result goes to y[6j] (the rest of y is 0)
     const bool head = i % 6 == 0 && i + 5 < n;
     y[i] = head ? gmx_lstm_adam_step(x[i], x[i + 1], x[i + 2], x[i + 3], x[i + 4], x[i + 5]) : 0.0f;
+    return;
+  }
+  if (what == 12) {
+    // x[8j .. 8j+7] = {x1, x2, x, p, next4, avail, 0, 0}: next4 holds the next four input bytes, the first in its
+    // low byte, of which the input has only `avail` (0 .. 4).  y[8j .. 8j+7] = {bit, x1, x2, x, consumed, pr, 0, 0}.
+    if (i % 8 != 0) return;  // (the tuple's first thread writes all of it)
+    if (i + 7 >= n) {
+      for (uint64_t k = i; k < n; ++k) y[k] = 0.0f;
+      return;
+    }
+    const uint32_t next4 = gmx_f2u(x[i + 4]), avail = gmx_f2u(x[i + 5]);
+    uint8_t in[4];
+    for (int k = 0; k < 4; ++k) in[k] = (uint8_t)(next4 >> (8 * k));
+    GmxCoderState st = {gmx_f2u(x[i]), gmx_f2u(x[i + 1]), gmx_f2u(x[i + 2]), 0u};
+    const float p = x[i + 3];
+    const uint32_t bit = gmx_coder_decode(&st, p, in, avail < 4u ? avail : 4u);
+    const uint32_t out[8] = {bit, st.x1, st.x2, st.x, st.pos, gmx_coder_discretize(p), 0u, 0u};
+    for (int k = 0; k < 8; ++k) y[i + k] = gmx_u2f(out[k]);
+    return;
+  }
+  if (what == 13) {
+    // x[260j .. 260j+259] = {top, bot, 0, 0, ppm[256]} with 0 <= bot <= top <= 255 (anything else answers nothing).
+    // y[260j .. 260j+2] = {wrote, slot, active}, the rest of y is 0; slot and active start from sentinels, so a
+    // walk that writes nothing shows them.
+    const uint64_t k = i % 260;
+    const bool whole = i - k + 259 < n;
+    if (whole && k >= 1 && k <= 2) return;  // (the case's first thread writes them)
+    if (!whole || k != 0) {
+      y[i] = 0.0f;
+      return;
+    }
+    const GmxCoderWalk w = {(int32_t)gmx_f2u(x[i]), (int32_t)gmx_f2u(x[i + 1])};
+    float slot = gmx_u2f(GMX_PROBE_WALK_SENTINEL);
+    bool active = true, wrote = false;
+    if (w.bot >= 0 && w.bot <= w.top && w.top <= 255) wrote = gmx_coder_walk_predict(&w, x + i + 4, &slot, &active);
+    y[i] = gmx_u2f(wrote ? 1u : 0u);
+    y[i + 1] = slot;
+    y[i + 2] = gmx_u2f(active ? 1u : 0u);
     return;
   }
   y[i] = gmx_math_unary(x[i], what, tab);

@@ -26,6 +26,11 @@ def u32(x):
     return np.ascontiguousarray(x, np.float32).view(np.uint32)
 
 
+def discretize(p):
+    """Decoder::Discretize: float multiply, float add, truncation (a scalar or an array of float32)."""
+    return (F32(1) + F32(65534) * np.asarray(p, F32)).astype(np.uint32)
+
+
 class PyDecoder:
     """coder/decoder.cpp.  state: (x1, x2, x, pos) to resume from (ReadCheckpoint plus the read position)."""
 
@@ -45,7 +50,10 @@ class PyDecoder:
         return self.data[self.pos - 1]
 
     def next(self, p):
-        pr = int(F32(1) + F32(65534) * F32(p))   # Discretize: float multiply, float add, truncation
+        return self.next_pr(int(discretize(p)))
+
+    def next_pr(self, pr):
+        """Decode behind Discretize."""
         r = self.x2 - self.x1
         xmid = (self.x1 + (r >> 16) * pr + (((r & 0xFFFF) * pr) >> 16)) & 0xFFFFFFFF
         if self.x <= xmid:
@@ -104,6 +112,10 @@ class PyWalk:
             self.bot = self.mid + 1
         else:
             self.top = self.mid
+        self.predict(ppm)
+
+    def predict(self, ppm):
+        """The bit prediction of [bot, top]; returns whether the slot was written."""
         self.mid = self.bot + (self.top - self.bot) // 2
         num = F32(0)
         for v in ppm[self.mid + 1:self.top + 1]:
@@ -112,10 +124,12 @@ class PyWalk:
         for v in ppm[self.bot:self.mid + 1]:
             denom = F32(denom + v)
         self.active = False
+        self.num, self.denom = num, denom
         if denom != 0:
             p = F32(num / denom)
             self.slot = logit(p)
             self.active = bool(p != F32(0.5))
+        return bool(denom != 0)
 
 
 class Stream:
@@ -133,16 +147,17 @@ class Stream:
 class Rig:
     """One chain: the mixers, the Indirect models, the Match models, the context bank, optionally the LSTM, and the
     lock-step object with all of them attached.  shape "small": 40 inputs, six general mixers, five Indirect and eight
-    Match models, ctx_tiny's 17 variables; "stock": the reference's own shape."""
+    Match models, ctx_tiny's 17 variables; "stock": the reference's own shape.  n_inputs: another input count for
+    "small" (the models keep their slots); ppmd_slot: another free slot for ModPPMD."""
 
-    def __init__(self, gpu, shape, S, with_lstm=False, decoder=True, lstm_seed=23):
+    def __init__(self, gpu, shape, S, with_lstm=False, decoder=True, lstm_seed=23, n_inputs=None, ppmd_slot=None):
         self.S, self.shape = S, shape
         self.lg = None
         if shape == "small":
             f = cc.fixture("ctx_tiny")
             fm = mc.fixture("match_k8")
             _, z = goldenlib.load("ind_tiny_dense")
-            self.topo = Topology(40, tm.MIXERS, (1,))
+            self.topo = Topology(40 if n_inputs is None else n_inputs, tm.MIXERS, (1,))
             self.mixer_route = [-1, 13, -1, -1, 14, 16]   # columns 0, 2, 3 are longest_match (tm.COLS)
             self.ind_route = [0, 1, 2, 5, 4]
             self.match_route = [4, 11, 3, 5, 12, 2, 9, 7]
@@ -176,7 +191,10 @@ class Rig:
                 self.cs = gpu.ChainStep(self.mg, self.ig, self.lg, lstm_slot=1, mixer_ctx_col=22, ind_ctx_col=16)
             else:
                 self.cs = gpu.ChainStep(self.mg, self.ig)
-        assert self.ppmd_slot not in used
+        assert n_inputs is None or shape == "small"
+        if ppmd_slot is not None:
+            self.ppmd_slot = ppmd_slot
+        assert self.ppmd_slot not in used and 0 <= self.ppmd_slot < self.topo.n_inputs
         self.cs.attach_match(self.xg, self.cols)
         self.cs.attach_ctx(self.cg, self.mixer_route, self.ind_route, self.match_route)
         if decoder:
@@ -343,3 +361,263 @@ def assert_same(st_a, st_b, rig_a, rig_b, streams=None):
         ea, eb = rig_a.exports(s), rig_b.exports(s)
         for k in ea:
             assert ea[k] == eb[k], (k, s)
+
+
+# ---- operands for the device probe of gmx_coder.h (gmx_debug_math_probe, what = 12 and 13; tests/test_gpu_coder_device.py) --
+# A decode tuple is six words {x1, x2, x, p (bit pattern), next4, avail}: next4 packs the next four input bytes, the
+# first in its low byte, of which the input holds only `avail`.  What Decode makes of it is six words too:
+# {bit, x1, x2, x, bytes consumed, pr}.
+PROBE_DECODE, PROBE_WALK = 12, 13
+WALK_SENTINEL = 0xC2F60000                 # -123.0f: what the probe presets the slot to
+EDGE_PR = (7, 8, 32767, 32768, 32769, 65527, 65528)
+EDGE_RANGES = (0, 1, 255, 256, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 32) - 1)
+M32 = 0xFFFFFFFF
+
+
+def f2u(v):
+    return int(F32(v).view(np.uint32))
+
+
+def u2f(u):
+    return np.uint32(u).view(F32)
+
+
+def p_ends(pr):
+    """The smallest and the largest float p in [0, 1] that Discretize takes to pr: it never decreases as p grows (a
+    rounded multiply and a rounded add), so each end is a bisection over the bit patterns of the positive floats."""
+    lo, hi = 0, f2u(1.0)                   # the least u with discretize(u) >= pr
+    while lo < hi:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if int(discretize(u2f(mid))) >= pr else (mid + 1, hi)
+    first = lo
+    lo, hi = 0, f2u(1.0)                   # the least u with discretize(u) > pr
+    while lo < hi:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if int(discretize(u2f(mid))) > pr else (mid + 1, hi)
+    assert int(discretize(u2f(first))) == pr == int(discretize(u2f(lo - 1))), pr
+    assert first == 0 or int(discretize(u2f(first - 1))) == pr - 1
+    assert int(discretize(u2f(lo))) == pr + 1
+    return first, lo - 1
+
+
+def edge_p():
+    """Bit patterns: both ends of every EDGE_PR, the clamps of Predictor::Predict -+ 1 ulp, 0.5."""
+    out = [u for pr in EDGE_PR for u in p_ends(pr)]
+    for v in (0.0001, 0.9999):
+        out += [f2u(v) - 1, f2u(v), f2u(v) + 1]
+    out.append(f2u(0.5))
+    return sorted(set(out))
+
+
+def xmid_of(x1, x2, pr):
+    r = x2 - x1
+    return (x1 + (r >> 16) * pr + (((r & 0xFFFF) * pr) >> 16)) & M32
+
+
+def edge_x1(r):
+    """Where a range of width r lies: at byte-aligned bases (a boundary of the top byte -- or, after one, two, three
+    shifts, of the byte that is the top one by then -- outside it), straddling such a boundary, ending just below one,
+    beginning on one, and at the top of the 32 bits."""
+    out = [0, 0x12000000, 0x12340000, 0x12345600, 0x12345678, 0xFF000000, M32 - r]
+    for q in (0x01000000, 0x80000000, 0x13000000, 0x12350000, 0x12345700, 0xFFFFFF00):
+        out += [q - (r >> 1) - 1, q - r - 1, q]
+    return sorted({v for v in out if 0 <= v and v + r <= M32})
+
+
+def edge_tuples():
+    """The constructed operands of Decode, [N][6] uint32: EDGE_RANGES x edge_x1 x edge_p x {x1, xmid - 1, xmid, xmid + 1,
+    x2} (where inside [x1, x2]) x avail 0 .. 4, the input bytes seeded and never 0 (a read past the end shows)."""
+    rng = np.random.default_rng(1234)
+    ps = [(u, int(discretize(u2f(u)))) for u in edge_p()]
+    rows = []
+    for r in EDGE_RANGES:
+        for x1 in edge_x1(r):
+            x2 = x1 + r
+            for pu, pr in ps:
+                xm = xmid_of(x1, x2, pr)
+                for x in sorted({v for v in (x1, xm - 1, xm, xm + 1, x2) if x1 <= v <= x2}):
+                    for avail in range(5):
+                        rows.append((x1, x2, x, pu, 0, avail))
+    t = np.array(rows, np.uint32)
+    t[:, 4] = rng.integers(1, 256, (len(t), 4), dtype=np.uint32) @ np.array([1, 1 << 8, 1 << 16, 1 << 24], np.uint32)
+    return t
+
+
+def random_tuples(n, seed):
+    """x1 <= x <= x2 with the range's width spread over all 33 magnitudes; p from all of (0, 1), from the clamped
+    interval's bit patterns, and the clamps and 0.5 themselves."""
+    rng = np.random.default_rng(seed)
+    r = rng.integers(0, 1 << 32, n, dtype=np.uint64) >> rng.integers(0, 33, n, dtype=np.uint64)
+    x1 = (rng.random(n) * (M32 - r + 1).astype(np.float64)).astype(np.uint64)
+    x1 = np.minimum(x1, M32 - r)
+    x = x1 + (rng.integers(0, 1 << 32, n, dtype=np.uint64) % (r + 1))
+    lo, hi = f2u(0.0001), f2u(0.9999)
+    p = rng.random(n, dtype=np.float32).view(np.uint32)
+    kind = rng.integers(0, 8, n)
+    p = np.where(kind < 3, rng.integers(lo, hi + 1, n, dtype=np.uint32), p)
+    p = np.where(kind == 7, np.array([lo, hi, f2u(0.5), lo + 1], np.uint32)[rng.integers(0, 4, n)], p)
+    t = np.zeros((n, 6), np.uint32)
+    t[:, 0], t[:, 1], t[:, 2], t[:, 3] = x1, x1 + r, x, p
+    t[:, 4] = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    t[:, 5] = rng.integers(0, 5, n)
+    assert (t[:, 0] <= t[:, 2]).all() and (t[:, 2] <= t[:, 1]).all()
+    return t
+
+
+def trace_tuples(z):
+    """tests/golden/decoder_trace.npz (the reference's own Decoder, recorded) as probe operands: for every bit t the state
+    after t - 1, p[t] and the next four input bytes -> (tuples [N][6], expected [N][6]).  Bit and state are the recorded
+    ones.  The trace has no read position: it is PyDecoder's, whose bits and states must first equal the recorded ones;
+    pr is Discretize of the recorded p.  Behind a bit that shifted nothing follows the same range with x on the boundary
+    that the recorded state names (below)."""
+    tup, exp = [], []
+    for name in (str(n) for n in z["names"]):
+        data, pu = bytes(z[name + "_input"]), z[name + "_p"].astype(np.uint32)
+        d = PyDecoder(data)
+        for t in range(len(pu)):
+            before = d.state()
+            bit = d.next(pu[t].view(F32))
+            x1, x2, x = (int(v) for v in z[name + "_state"][t])
+            assert (bit, d.x1, d.x2, d.x) == (int(z[name + "_bits"][t]), x1, x2, x), (name, t)
+            pos = before[3]
+            nxt = data[pos:pos + 4]
+            rest = (int(pu[t]), int.from_bytes(nxt.ljust(4, b"\xa5"), "little"), len(nxt))
+            pr = int(discretize(pu[t].view(F32)))
+            tup.append(before[:3] + rest)
+            exp.append((bit, x1, x2, x, d.pos - pos, pr))
+            # A random x never lies on the comparison's boundary, but the recorded state names it: where the bit
+            # shifted nothing (x is unchanged and not 0), a recorded 1 left x2_ = xmid and a recorded 0 left
+            # x1_ = xmid + 1.  The same range with x on that value gives the recorded bit, x1_ and x2_ again.
+            if x == before[2] != 0:
+                edge = x2 if bit else x1
+                tup.append(before[:2] + (edge,) + rest)
+                exp.append((bit, x1, x2, edge, 0, pr))
+    return np.array(tup, np.uint32), np.array(exp, np.uint32)
+
+
+def decode_expected(t):
+    """PyDecoder on every tuple of t -> [N][6] uint32 {bit, x1, x2, x, consumed, pr}."""
+    pr = discretize(t[:, 3].view(F32))     # (float32 multiply and add, as PyDecoder.next's)
+    out = []
+    for (x1, x2, x, _, next4, avail), k in zip(t.tolist(), pr.tolist()):
+        d = PyDecoder(next4.to_bytes(4, "little")[:avail], (x1, x2, x, 0))
+        bit = d.next_pr(k)
+        out.append((bit, d.x1, d.x2, d.x, d.pos, k))
+    return np.array(out, np.uint32).reshape(-1, 6)
+
+
+def decode_census(t):
+    """What the tuples of t exercise, by PyDecoder alone: how many shift 0 .. 4 bytes, how many have x == xmid,
+    x == xmid + 1, a range below 65 536, a shift that reads past the input's end."""
+    c = dict(shifts=[0] * 5, x_is_xmid=0, x_is_xmid_plus_1=0, narrow=0, reads_past_end=0)
+    pr = discretize(t[:, 3].view(F32)).tolist()
+
+    def bit_at(x1, x2, x, k):
+        return PyDecoder(b"", (x1, x2, x, 0)).next_pr(k)
+    for (x1, x2, x, _, next4, avail), k in zip(t.tolist(), pr):
+        d = PyDecoder(b"\1\1\1\1", (x1, x2, x, 0))     # four spare bytes: pos counts the shifts
+        bit = d.next_pr(k)
+        c["shifts"][d.pos] += 1
+        # x == xmid: the last x that decodes a 1; x == xmid + 1: the first that decodes a 0
+        c["x_is_xmid"] += bit == 1 and x < M32 and bit_at(x1, x2, x + 1, k) == 0
+        c["x_is_xmid_plus_1"] += bit == 0 and x > 0 and bit_at(x1, x2, x - 1, k) == 1
+        c["narrow"] += (x2 - x1) >> 16 == 0
+        c["reads_past_end"] += d.pos > avail
+    return c
+
+
+def probe_decode(L, t):
+    """The tuples of t through the device's gmx_coder_decode -> [N][6] uint32 as decode_expected's."""
+    x = np.zeros((len(t), 8), np.uint32)
+    x[:, :6] = t
+    y = np.full_like(x, GARBAGE)
+    assert L.gmx_debug_math_probe(0, x.ctypes.data, y.ctypes.data, x.size, PROBE_DECODE) == 0
+    assert not y[:, 6:].any()
+    return y[:, :6]
+
+
+def walk_pairs():
+    """The 255 ranges [bot, top] with top > bot that eight bits can lead to."""
+    out, level = [], [(255, 0)]
+    while level:
+        out += level
+        nxt = []
+        for top, bot in level:
+            mid = bot + (top - bot) // 2
+            nxt += [(t, b) for t, b in ((mid, bot), (top, mid + 1)) if t > b]
+        level = nxt
+    assert len(out) == 255 == len(set(out))
+    return out
+
+
+def walk_distributions():
+    """[(name, ppm[256] float32)]: test_coder.cpp's distributions, then subnormal masses, a single mass, two masses
+    1 ulp apart that a bit at every depth separates, and 200 random ones with zeros and mixed magnitudes."""
+    out = [("uniform", np.full(256, F32(1) / F32(256), F32))]
+    r = [88172645463325252]
+
+    def rnd():                             # test_coder.cpp's xorshift64
+        r[0] ^= (r[0] << 13) & 0xFFFFFFFFFFFFFFFF
+        r[0] ^= r[0] >> 7
+        r[0] ^= (r[0] << 17) & 0xFFFFFFFFFFFFFFFF
+        return F32(F32((r[0] >> 40) & 0xFFFF) / F32(65536))
+    out.append(("upper half zero", np.array([F32(rnd() + F32(1e-3)) if i < 128 else F32(0) for i in range(256)], F32)))
+    ppm = np.array([F32(rnd() * F32(1e-7 if i % 7 == 0 else 1e3 if i % 5 == 0 else 1.0)) for i in range(256)], F32)
+    ppm[[0, 16, 17, 32, 33, 34, 35, 64, 65, 66, 67, 68, 69, 70, 71, 200, 254, 255]] = 0
+    out.append(("scattered zeros", ppm))
+    out.append(("all zero", np.zeros(256, F32)))
+    rng = np.random.default_rng(77)
+    # 1e-45 .. 1e-38: bit patterns 1 .. 0x7fffff, the magnitude spread evenly over the 23 binades of the subnormals
+    sub = ((1 << rng.integers(0, 23, 256)) | rng.integers(0, 1 << 22, 256)) & 0x7FFFFF
+    out.append(("subnormal masses", np.maximum(sub, 1).astype(np.uint32).view(F32)))
+    tiny = np.ones(256, F32)               # the quotient itself is subnormal: 2^-127 over 128
+    tiny[128:] = 0
+    tiny[255] = u2f(0x00400000)
+    out.append(("subnormal quotient", tiny))
+    for at in (0, 77, 255):
+        one = np.zeros(256, F32)
+        one[at] = 1
+        out.append(("single mass at %d" % at, one))
+    a, b = F32(0.3), u2f(f2u(0.3) + 1)
+    for depth in range(8):
+        for lo_mass, hi_mass in ((a, b), (b, a)):
+            two = np.zeros(256, F32)
+            two[0], two[(256 >> depth) - 1] = lo_mass, hi_mass
+            out.append(("two masses 1 ulp apart, depth %d" % depth, two))
+    for i in range(200):
+        ppm = rng.random(256, dtype=np.float32)
+        if i % 4 == 1:
+            ppm *= F32(10) ** rng.integers(-8, 4, 256).astype(F32)
+        if i % 4 == 2:
+            ppm[rng.random(256) < 0.5] = 0
+        if i % 4 == 3:
+            lo = int(rng.integers(0, 200))
+            ppm[lo:lo + int(rng.integers(1, 56))] = 0
+        out.append(("random %d" % i, ppm.astype(F32)))
+    return out
+
+
+def walk_expected(ppm):
+    """PyWalk on the 255 ranges over ppm -> ([255][3] uint32 {wrote, slot bits, active}, [(num, denom, p or None)])."""
+    out, seen = np.zeros((255, 3), np.uint32), []
+    for i, (top, bot) in enumerate(walk_pairs()):
+        w = PyWalk()
+        w.top, w.bot, w.slot = top, bot, u2f(WALK_SENTINEL)
+        wrote = w.predict(ppm)
+        # (a walk that writes nothing leaves the probe's presets: the sentinel, active = 1)
+        out[i] = (1, f2u(w.slot), w.active) if wrote else (0, WALK_SENTINEL, 1)
+        seen.append((w.num, w.denom, F32(w.num / w.denom) if wrote else None))
+    return out, seen
+
+
+def probe_walk(L, ppms):
+    """Every range of walk_pairs over every distribution of ppms ([D][256]) through the device's
+    gmx_coder_walk_predict -> [D][255][3] uint32."""
+    pairs = np.array(walk_pairs(), np.uint32)
+    x = np.zeros((len(ppms), 255, 260), np.uint32)
+    x[:, :, 0:2] = pairs
+    x[:, :, 4:] = np.ascontiguousarray(ppms, F32).view(np.uint32)[:, None, :]
+    y = np.full_like(x, GARBAGE)
+    assert L.gmx_debug_math_probe(0, x.ctypes.data, y.ctypes.data, x.size, PROBE_WALK) == 0
+    assert not y[:, :, 3:].any()
+    return y[:, :, :3]

@@ -121,6 +121,59 @@ def test_ragged_participation(gpu):
     b.close()
 
 
+def test_seventy_streams_two_tail_blocks(gpu):
+    """gmx_coder_tail_kernel takes a lane per stream: S = 70 is a full block and one with six live lanes, and the answer
+    area's parts (take | decoded | byte_p | state) lie at rounded offsets that S = 70 does not fill.  Three bytes.
+    Streams 0 .. 3 have inputs of 0, 1, 2 and 3 bytes (the four start bytes already read past the end), streams 64 and
+    69 -- the second block's first and last live lane -- 50 bytes, the others 20.  Streams 5 and 66 sit byte 1 out, one in
+    each block (in the yardstick they simply code two bytes): nothing of theirs is written by that call.  (Whether the
+    tail stamped them cannot be seen from here: this shape's wait is the stream's synchronisation, not the stamps'.)"""
+    S, NB, OUT = 70, 3, (5, 66)
+    ppm = dc.make_ppm(S, NB, 23)
+    rng = np.random.default_rng(70)
+    lens = [0, 1, 2, 3] + [20] * (S - 4)
+    lens[64] = lens[69] = 50
+    inputs = [bytes(rng.integers(0, 256, n, dtype=np.uint8)) for n in lens]
+    a = dc.Rig(gpu, "small", S, decoder=False)
+    st_a = run(a, inputs, [NB - 1 if s in OUT else NB for s in range(S)], ppm, False)
+    assert [st_a[s].states[-1][3] for s in range(4)] == [0, 1, 2, 3]
+    b = dc.Rig(gpu, "small", S)
+    st_b = dc.decode_streams(b, inputs)
+    for k in range(NB):
+        group = [s for s in range(S) if k != 1 or s not in OUT]
+        kept = {s: (int(b.cs.decoded[s]), b.cs.byte_p[s].tobytes(), b.cs.decoder_state(s)) for s in OUT}
+        dc.byte_round(b, st_b, group, ppm)
+        if k == 1:
+            for s in OUT:
+                assert (int(b.cs.decoded[s]), b.cs.byte_p[s].tobytes(), b.cs.decoder_state(s)) == kept[s], s
+                assert kept[s] == (st_b[s].bytes[0], np.array(st_b[s].p[0], np.uint32).tobytes(), st_b[s].states[0]), s
+    dc.learn_only(b, st_b, range(S))
+    dc.assert_same(st_a, st_b, a, b)
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("n_inputs, slot", [(None, 37), (72, 70)], ids=["second_mask_word", "second_row_trip"])
+def test_ppmd_slot_position(gpu, n_inputs, slot):
+    """gmx_coder_step_kernel writes the prediction row 64 slots a trip and the mask word of ModPPMD's slot.  Slot 37 of
+    the 40 inputs: the slot's word is mask word 1.  Slot 70 of 72 inputs (n_pad = 72: the row takes two trips, the mask
+    three words): the slot lies in the second trip and in word 2.  Six bytes of make_ppm; stream 1's input is all
+    zeros, so x is 0, every bit decodes as 1, and its slot is active (bytes 0, 1, 3, 5), inactive (the uniform byte 2)
+    and silent (byte 4 has no mass above 127, where the first 1 leads)."""
+    S, NB = 2, 6
+    ppm = dc.make_ppm(S, NB, 29)
+    inputs = [ragged_inputs(1)[0], bytes(40)]
+    rigs = [dc.Rig(gpu, "small", S, decoder=on, n_inputs=n_inputs, ppmd_slot=slot) for on in (False, True)]
+    a, b = rigs
+    assert a.ppmd_slot == slot and (a.cs.predictions.shape[1] > 64) == (slot >= 64) and slot >> 5 == a.cs.mask_words - 1
+    st_a = run(a, inputs, [NB] * S, ppm, False)
+    assert st_a[1].bytes == [255] * NB
+    st_b = run(b, inputs, [NB] * S, ppm, True)
+    dc.assert_same(st_a, st_b, a, b)
+    a.close()
+    b.close()
+
+
 def test_resume_in_a_fresh_object_and_two_objects_in_halves(gpu):
     """Six bytes, then every bank moves through its group export / import into a fresh chain whose decoders resume from
     decoder_state, six more bytes: equal to twelve bytes in one go.  And two objects driven alternately in launch / wait
