@@ -25,6 +25,7 @@
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
+#include "gmx_batch_rows.h"
 #include "gmx_ckpt.h"
 #include "gmx_ckpt_stage.h"
 #include "gmx_ind_ckpt.h"
@@ -241,6 +242,159 @@ static int xfer_wait(GmxXfer& x) {
   return GMX_OK;
 }
 
+// ---- the record batch itself: what gmx_batch, gmx_ind_batch, gmx_lstm_batch, gmx_match_batch and gmx_ctx_batch
+// share.  Each of them IS a GmxBatchCore plus its typed array pointers, which the launch code reads; the column table
+// (gmx_batch_rows.h) points at them, and everything below works through the table ----------------------------------
+struct GmxBatchCore;
+// What a batch needs of the bank that owns it (a member of gmx_group, gmx_indirect, gmx_lstm, gmx_match, gmx_ctx).
+struct GmxBatchBank {
+  void* self = nullptr;                        // the bank, as the batches' typed back-pointers name it
+  int device = 0;
+  hipStream_t* main = nullptr;                 // its compute stream (an address: a CU mask replaces the stream)
+  hipStream_t *up = nullptr, *down = nullptr;  // its transfer streams; null: the bank has ONE stream, copies ride on it
+  std::vector<GmxBatchCore*> batches;          // live batches; shells once the bank is gone (batch_bank_detach_all)
+};
+static void batch_bank_init(GmxBatchBank& k, void* self, int device, hipStream_t* main, hipStream_t* up = nullptr,
+                            hipStream_t* down = nullptr) {
+  k.self = self;
+  k.device = device;
+  k.main = main;
+  k.up = up;
+  k.down = down;
+}
+struct GmxBatchCore {
+  int S = 0;              // streams covered
+  uint64_t max_rows = 0;  // records per stream
+  GmxBatchCols cols;
+  GmxXfer x;              // ordering of this batch's transfers against the kernels that use its device arrays
+  // Liveness.  A batch whose bank was destroyed first is a shell: it keeps its buffers until its own destroy, and
+  // every other call on it fails with GMX_ERR_INVALID.  `back` is the address of the owning struct's typed pointer to
+  // its bank (b->g, b->ib, ...), which the launch code tests; batch_core_set_bank is the one writer of both.
+  GmxBatchBank* bank = nullptr;
+  void** back = nullptr;
+};
+static void batch_core_set_bank(GmxBatchCore& c, GmxBatchBank* k) {
+  c.bank = k;
+  *c.back = k ? k->self : nullptr;
+}
+// Off its bank's list and a shell from now on (its arrays stay until batch_core_free).
+static void batch_core_detach(GmxBatchCore& c) {
+  if (!c.bank) return;
+  auto& v = c.bank->batches;
+  v.erase(std::remove(v.begin(), v.end(), &c), v.end());
+  batch_core_set_bank(c, nullptr);
+}
+static void batch_bank_detach_all(GmxBatchBank& k) {  // the bank is being destroyed
+  while (!k.batches.empty()) batch_core_detach(*k.batches.back());
+}
+// Everything of a batch but the owning struct itself.
+static void batch_core_free(GmxBatchCore& c) {
+  if (GmxBatchBank* k = c.bank) {
+    (void)hipSetDevice(k->device);
+    hipStream_t busy[] = {*k->main, k->up ? *k->up : nullptr, k->down ? *k->down : nullptr};
+    for (hipStream_t s : busy)
+      if (s) (void)hipStreamSynchronize(s);
+    batch_core_detach(c);
+  }
+  for (const GmxBatchCol& col : c.cols) {
+    if (*col.dev) (void)hipFree(*col.dev);
+    if (col.host && *col.host) (void)hipHostFree(*col.host);
+  }
+  xfer_free(c.x);
+}
+#define BCHK(call)                                           \
+  do {                                                       \
+    hipError_t e_ = (call);                                  \
+    if (e_ != hipSuccess) {                                  \
+      int r_ = hip_fail(e_, #call);                          \
+      return e_ == hipErrorOutOfMemory ? GMX_ERR_NOMEM : r_; \
+    }                                                        \
+  } while (0)
+// The pinned array behind `slot` (the address of a typed h_ pointer), zero-filled when it is made; null for a shell,
+// for a column that is not in the table, and when pinned memory has run out.
+static void* batch_core_host(GmxBatchCore& c, const void* slot) {
+  if (!c.bank) return nullptr;
+  for (const GmxBatchCol& col : c.cols) {
+    if (col.host != slot) continue;
+    if (!*col.host) {
+      const size_t bytes = gmx_col_host_bytes(col, c.S, c.max_rows);
+      if (hipSetDevice(c.bank->device) != hipSuccess) return nullptr;
+      void* p = nullptr;
+      if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+      }
+      memset(p, 0, bytes);
+      *col.host = p;
+    }
+    return *col.host;
+  }
+  return nullptr;
+}
+// The device arrays of the table (a per-stream column starts zeroed), the pinned ones too with host_at_create (their
+// accessors then never allocate), the events, and the place on the bank's list.  `c.cols` and `c.back` are set; after
+// a failure the caller frees the batch.
+static int batch_core_alloc(GmxBatchCore& c, GmxBatchBank* k, int S, uint64_t max_rows, bool host_at_create) {
+  HIPCHK(hipSetDevice(k->device));
+  c.S = S;
+  c.max_rows = max_rows;
+  k->batches.push_back(&c);
+  batch_core_set_bank(c, k);
+  for (const GmxBatchCol& col : c.cols) {
+    const size_t bytes = gmx_col_dev_bytes(col, S, max_rows);
+    if (!bytes) continue;
+    BCHK(hipMalloc(col.dev, bytes));
+    if (col.per_stream) BCHK(hipMemset(*col.dev, 0, bytes));
+  }
+  for (const GmxBatchCol& col : c.cols)
+    if (host_at_create && col.host && !batch_core_host(c, col.host)) return GMX_ERR_NOMEM;
+  return xfer_init(c.x);
+}
+// The first n records of every stream, up or down, in the table's order.  A bank with transfer streams sends a big
+// transfer over one of them, beside its kernels (xfer_begin_upload / xfer_begin_download); a bank with one stream
+// copies on it: everything queued on the bank's stream after an upload sees the records, and a download stands behind
+// the kernels that wrote the results.
+static int batch_core_transfer(GmxBatchCore* c, uint64_t n, GmxColDir dir) {
+  if (!c || !c->bank || n > c->max_rows) return GMX_ERR_INVALID;
+  if (n == 0) return GMX_OK;
+  GmxBatchBank* k = c->bank;
+  HIPCHK(hipSetDevice(k->device));
+  for (const GmxBatchCol& col : c->cols)
+    if (col.dir == dir && !batch_core_host(*c, col.host)) return GMX_ERR_NOMEM;
+  const bool up = dir == GMX_COL_UP;
+  const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  hipStream_t main = *k->main, st = main;
+  if (k->up) {
+    // (small transfers stay on the bank's stream: the cross-stream hand-shakes would cost more than the copies could
+    // ever overlap)
+    const size_t bytes = (size_t)c->S * n * gmx_cols_row_bytes(c->cols, dir);
+    int rc = up ? xfer_begin_upload(c->x, main, k->up, bytes, &st) : xfer_begin_download(c->x, main, k->down, bytes, &st);
+    if (rc) return rc;
+  }
+  for (const GmxBatchCol& col : c->cols) {
+    if (col.dir != dir || col.per_stream) continue;
+    void *dst = up ? *col.dev : *col.host, *src = up ? *col.host : *col.dev;
+    const GmxRowCopy r = gmx_row_copy(c->S, c->max_rows, n, col.row_bytes);
+    if (r.height)
+      HIPCHK(hipMemcpy2DAsync(dst, r.pitch, src, r.pitch, r.width, r.height, kind, st));
+    else
+      HIPCHK(hipMemcpyAsync(dst, src, r.bytes, kind, st));
+  }
+  for (const GmxBatchCol& col : c->cols) {
+    if (col.dir != dir || !col.per_stream) continue;
+    void *dst = up ? *col.dev : *col.host, *src = up ? *col.host : *col.dev;
+    HIPCHK(hipMemcpyAsync(dst, src, gmx_col_host_bytes(col, c->S, c->max_rows), kind, st));
+  }
+  return up ? xfer_end_upload(c->x, main, st) : xfer_end_download(c->x, st);
+}
+// The host waits for THIS batch's queued work: its upload, the device work that used it, its download.  (Work on
+// other batches of the bank keeps running.)
+static int batch_core_wait(GmxBatchCore* c) {
+  if (!c || !c->bank) return GMX_ERR_INVALID;
+  HIPCHK(hipSetDevice(c->bank->device));
+  return xfer_wait(c->x);
+}
+
 
 // Per-stream counts of a launch over streams of different lengths (GmxRunArgs::T_list and its cousins): staging
 // slots used in turn, a slot reused only when the launch that read it is done.
@@ -344,7 +498,7 @@ struct gmx_group {
   unsigned run_seq = 0;
   hipEvent_t tm0 = nullptr, tm1 = nullptr;  // gmx_group_timer_*
   gmx_batch* one = nullptr;        // 1-bit batch (one record per stream) of the per-bit surface
-  std::vector<gmx_batch*> batches; // live batches; orphaned (b->g = nullptr) when the group dies
+  GmxBatchBank bb;                 // live batches; orphaned (b->g = nullptr) when the group dies
   std::vector<struct GmxSession*> sessions;  // per stream, lazily: persistent per-bit kernels
   std::vector<struct gmx_lockstep*> locksteps;  // live lock-step objects; orphaned (ls->g = nullptr) when the group dies
   bool banks_in_use_by_dead_kernel = false;  // a persistent wave that stopped answering may still hold them: never freed
@@ -360,10 +514,9 @@ struct gmx_group {
   struct GmxCkptState* ckpt = nullptr;  // gmx_group_export / gmx_group_import: chunk list and staging (gmx_ckpt.inc), lazily
 };
 
-struct gmx_batch {
+struct gmx_batch : GmxBatchCore {  // (S: g->S, or 1 for the per-bit batch)
   gmx_group* g = nullptr;
-  int S = 0;                       // streams covered (g->S, or 1 for the per-bit batch)
-  uint64_t max_bits = 0;
+  uint64_t& max_bits = max_rows;   // (the name the launch code reads it by)
   unsigned flags = 0;
   // device
   float* d_pred = nullptr;
@@ -386,7 +539,6 @@ struct gmx_batch {
   float* h_p = nullptr;
   float* h_out = nullptr;
   float* h_last = nullptr;
-  GmxXfer x;  // ordering of this batch's transfers against the kernels that use its device arrays
 };
 
 // lock-step stepping of all streams, one hipGraph per half step (gmx_lockstep.inc)
@@ -615,6 +767,7 @@ extern "C" int gmx_group_create(gmx_group** out, const gmx_topology* topo, int n
   gmx_group* g = new (std::nothrow) gmx_group();
   if (!g) return GMX_ERR_NOMEM;
   g->device = device;
+  batch_bank_init(g->bb, g, device, &g->stream, &g->up_stream, &g->down_stream);
   g->S = n_streams;
   g->topo = td;
   g->lds_bytes = td.lds_total * 4u;
@@ -661,8 +814,7 @@ extern "C" void gmx_group_destroy(gmx_group* g) {
   // gmx_batch_destroy, but every call on them fails with GMX_ERR_INVALID from now on.
   for (gmx_lockstep* ls : g->locksteps) ls->g = nullptr;  // their calls fail from now on; gmx_lockstep_destroy frees them
   g->locksteps.clear();
-  for (gmx_batch* b : g->batches) b->g = nullptr;
-  g->batches.clear();
+  batch_bank_detach_all(g->bb);
   // (a persistent wave that stopped answering and is still resident reads the topology and writes rows and latch:
   // leaked rather than freed under a running kernel)
   if (!g->banks_in_use_by_dead_kernel) {
@@ -1005,66 +1157,23 @@ static int launch_run(gmx_group* g, gmx_batch* b, int s0, int rec0, int ns, uint
 // ---- batches ---------------------------------------------------------------------------
 static void batch_free(gmx_batch* b) {
   if (!b) return;
-  if (b->g) {
-    (void)hipSetDevice(b->g->device);
-    if (b->g->stream) (void)hipStreamSynchronize(b->g->stream);
-    if (b->g->up_stream) (void)hipStreamSynchronize(b->g->up_stream);
-    if (b->g->down_stream) (void)hipStreamSynchronize(b->g->down_stream);
-    auto& v = b->g->batches;
-    v.erase(std::remove(v.begin(), v.end(), b), v.end());
-  }
-  void* dv[] = {b->d_pred, b->d_mask, b->d_ctx, b->d_bits, b->d_p, b->d_out, b->d_last,
-                b->d_rng, b->d_tcount, b->d_pstate, b->d_cstate};
-  for (void* p : dv)
-    if (p) (void)hipFree(p);
-  void* hv[] = {b->h_pred, b->h_mask, b->h_ctx, b->h_bits, b->h_p, b->h_out, b->h_last};
-  for (void* p : hv)
-    if (p) (void)hipHostFree(p);
-  xfer_free(b->x);
+  batch_core_free(*b);
   delete b;
 }
 
 static int batch_alloc(gmx_batch** out, gmx_group* g, int S, uint64_t max_bits, unsigned flags) {
   if (!out || !g || max_bits == 0) return GMX_ERR_INVALID;
   *out = nullptr;
-  HIPCHK(hipSetDevice(g->device));
   gmx_batch* b = new (std::nothrow) gmx_batch();
   if (!b) return GMX_ERR_NOMEM;
-  b->g = g;
-  b->S = S;
-  b->max_bits = max_bits;
+  b->back = (void**)&b->g;
   b->flags = flags;
-  const GmxTopoDev& t = g->topo;
-  const size_t R = (size_t)S * max_bits;
-#define BCHK(call)                                 \
-  do {                                             \
-    hipError_t e_ = (call);                        \
-    if (e_ != hipSuccess) {                        \
-      int r_ = hip_fail(e_, #call);                \
-      batch_free(b);                               \
-      return e_ == hipErrorOutOfMemory ? GMX_ERR_NOMEM : r_; \
-    }                                              \
-  } while (0)
-  BCHK(hipMalloc((void**)&b->d_pred, R * t.n_pad * sizeof(float)));
-  if (flags & GMX_BATCH_MASK) BCHK(hipMalloc((void**)&b->d_mask, R * t.mask_words * sizeof(uint32_t)));
-  // (+ one record: gmx_stock_kernel's plain build reads, and ignores, the context word behind its last bit)
-  BCHK(hipMalloc((void**)&b->d_ctx, (R + 1) * t.m * sizeof(uint32_t)));
-  BCHK(hipMalloc((void**)&b->d_bits, R));
-  BCHK(hipMalloc((void**)&b->d_p, R * sizeof(float)));
-  if (flags & GMX_BATCH_OUTPUTS) BCHK(hipMalloc((void**)&b->d_out, R * t.m * sizeof(float)));
-  if (flags & GMX_BATCH_LAST_OUTPUTS) {
-    BCHK(hipMalloc((void**)&b->d_last, (size_t)S * t.m * sizeof(float)));
-    BCHK(hipMemset(b->d_last, 0, (size_t)S * t.m * sizeof(float)));
+  gmx_mixer_batch_cols(b->cols, b, g->topo.n_pad, g->topo.m, g->topo.mask_words, flags);
+  int rc = batch_core_alloc(*b, &g->bb, S, max_bits, false);
+  if (rc) {
+    batch_free(b);
+    return rc;
   }
-#undef BCHK
-  {
-    int rcx = xfer_init(b->x);
-    if (rcx) {
-      batch_free(b);
-      return rcx;
-    }
-  }
-  g->batches.push_back(b);
   *out = b;
   return GMX_OK;
 }
@@ -1087,55 +1196,17 @@ extern "C" int gmx_batch_n_pad(const gmx_batch* b) { return (b && b->g) ? b->g->
 extern "C" int gmx_batch_mask_words(const gmx_batch* b) { return (b && b->g) ? b->g->topo.mask_words : GMX_ERR_INVALID; }
 extern "C" uint64_t gmx_batch_max_bits(const gmx_batch* b) { return b ? b->max_bits : 0; }
 
-template <typename T>
-static T* lazy_host(gmx_batch* b, T** slot, size_t count) {
-  if (!*slot) {
-    if (hipSetDevice(b->g->device) != hipSuccess) return nullptr;
-    void* p = nullptr;
-    if (hipHostMalloc(&p, count * sizeof(T), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    memset(p, 0, count * sizeof(T));
-    *slot = (T*)p;
-  }
-  return *slot;
-}
-
-extern "C" float* gmx_batch_predictions(gmx_batch* b) {
-  return (b && b->g) ? lazy_host(b, &b->h_pred, (size_t)b->S * b->max_bits * b->g->topo.n_pad) : nullptr;
-}
+extern "C" float* gmx_batch_predictions(gmx_batch* b) { return b ? (float*)batch_core_host(*b, &b->h_pred) : nullptr; }
 extern "C" uint32_t* gmx_batch_active_mask(gmx_batch* b) {
-  if (!b || !b->g || !(b->flags & GMX_BATCH_MASK)) return nullptr;
-  return lazy_host(b, &b->h_mask, (size_t)b->S * b->max_bits * b->g->topo.mask_words);
+  return b ? (uint32_t*)batch_core_host(*b, &b->h_mask) : nullptr;
 }
-extern "C" uint32_t* gmx_batch_contexts(gmx_batch* b) {
-  return (b && b->g) ? lazy_host(b, &b->h_ctx, (size_t)b->S * b->max_bits * b->g->topo.m) : nullptr;
-}
-extern "C" uint8_t* gmx_batch_bits(gmx_batch* b) {
-  return (b && b->g) ? lazy_host(b, &b->h_bits, (size_t)b->S * b->max_bits) : nullptr;
-}
-extern "C" const float* gmx_batch_p(gmx_batch* b) {
-  return (b && b->g) ? lazy_host(b, &b->h_p, (size_t)b->S * b->max_bits) : nullptr;
-}
+extern "C" uint32_t* gmx_batch_contexts(gmx_batch* b) { return b ? (uint32_t*)batch_core_host(*b, &b->h_ctx) : nullptr; }
+extern "C" uint8_t* gmx_batch_bits(gmx_batch* b) { return b ? (uint8_t*)batch_core_host(*b, &b->h_bits) : nullptr; }
+extern "C" const float* gmx_batch_p(gmx_batch* b) { return b ? (float*)batch_core_host(*b, &b->h_p) : nullptr; }
 extern "C" const float* gmx_batch_last_outputs(gmx_batch* b) {
-  if (!b || !b->g || !(b->flags & GMX_BATCH_LAST_OUTPUTS)) return nullptr;
-  return lazy_host(b, &b->h_last, (size_t)b->S * b->g->topo.m);
+  return b ? (float*)batch_core_host(*b, &b->h_last) : nullptr;
 }
-extern "C" const float* gmx_batch_outputs(gmx_batch* b) {
-  if (!b || !b->g || !(b->flags & GMX_BATCH_OUTPUTS)) return nullptr;
-  return lazy_host(b, &b->h_out, (size_t)b->S * b->max_bits * b->g->topo.m);
-}
-
-// Copy the first n_bits records of every stream (rows of a [S][max_bits][w] array).
-static hipError_t copy_rows(void* dst, const void* src, size_t elem_bytes, size_t w, gmx_batch* b,
-                            uint64_t n_bits, hipMemcpyKind kind, hipStream_t st) {
-  const size_t pitch = (size_t)b->max_bits * w * elem_bytes;
-  const size_t width = (size_t)n_bits * w * elem_bytes;
-  if (n_bits == b->max_bits || b->S == 1)
-    return hipMemcpyAsync(dst, src, b->S == 1 ? width : pitch * b->S, kind, st);
-  return hipMemcpy2DAsync(dst, pitch, src, pitch, width, (size_t)b->S, kind, st);
-}
+extern "C" const float* gmx_batch_outputs(gmx_batch* b) { return b ? (float*)batch_core_host(*b, &b->h_out) : nullptr; }
 
 // Device-side work on the group's stream has just been queued that reads or writes b's arrays.
 static int batch_note_device_use(gmx_batch* b) { return xfer_note_device_use(b->x, b->g->stream); }
@@ -1143,58 +1214,10 @@ static int batch_note_device_use(gmx_batch* b) { return xfer_note_device_use(b->
 // The copies run on the group's upload stream: behind the last kernel that used this batch's
 // arrays, beside whatever else the group's stream is running (the kernel of ANOTHER batch, in a
 // double-buffered loop).  Everything queued on the group's stream after this call sees the records.
-extern "C" int gmx_batch_upload(gmx_batch* b, uint64_t n_bits) {
-  if (!b || !b->g || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  gmx_group* g = b->g;
-  const GmxTopoDev& t = g->topo;
-  HIPCHK(hipSetDevice(g->device));
-  if (!gmx_batch_predictions(b) || !gmx_batch_contexts(b) || !gmx_batch_bits(b)) return GMX_ERR_NOMEM;
-  if ((b->flags & GMX_BATCH_MASK) && !gmx_batch_active_mask(b)) return GMX_ERR_NOMEM;
-  // (small transfers stay on the group's stream: the cross-stream hand-shakes would cost more than
-  // the copies could ever overlap)
-  const size_t bytes = (size_t)b->S * n_bits * ((size_t)t.n_pad * 4 + (size_t)t.m * 4 + 1 +
-                                                ((b->flags & GMX_BATCH_MASK) ? (size_t)t.mask_words * 4 : 0));
-  hipStream_t st = nullptr;
-  int rc = xfer_begin_upload(b->x, g->stream, &g->up_stream, bytes, &st);
-  if (rc) return rc;
-  HIPCHK(copy_rows(b->d_pred, b->h_pred, 4, t.n_pad, b, n_bits, hipMemcpyHostToDevice, st));
-  if (b->flags & GMX_BATCH_MASK)
-    HIPCHK(copy_rows(b->d_mask, b->h_mask, 4, t.mask_words, b, n_bits, hipMemcpyHostToDevice, st));
-  HIPCHK(copy_rows(b->d_ctx, b->h_ctx, 4, t.m, b, n_bits, hipMemcpyHostToDevice, st));
-  HIPCHK(copy_rows(b->d_bits, b->h_bits, 1, 1, b, n_bits, hipMemcpyHostToDevice, st));
-  return xfer_end_upload(b->x, g->stream, st);
-}
-
+extern "C" int gmx_batch_upload(gmx_batch* b, uint64_t n_bits) { return batch_core_transfer(b, n_bits, GMX_COL_UP); }
 // Behind everything queued on the group's stream so far, on the group's download stream.
-extern "C" int gmx_batch_download(gmx_batch* b, uint64_t n_bits) {
-  if (!b || !b->g || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  gmx_group* g = b->g;
-  const GmxTopoDev& t = g->topo;
-  HIPCHK(hipSetDevice(g->device));
-  if (!gmx_batch_p(b)) return GMX_ERR_NOMEM;
-  if ((b->flags & GMX_BATCH_OUTPUTS) && !gmx_batch_outputs(b)) return GMX_ERR_NOMEM;
-  if ((b->flags & GMX_BATCH_LAST_OUTPUTS) && !gmx_batch_last_outputs(b)) return GMX_ERR_NOMEM;
-  const size_t bytes = (size_t)b->S * n_bits * (4 + ((b->flags & GMX_BATCH_OUTPUTS) ? (size_t)t.m * 4 : 0));
-  hipStream_t st = nullptr;
-  int rc = xfer_begin_download(b->x, g->stream, &g->down_stream, bytes, &st);
-  if (rc) return rc;
-  HIPCHK(copy_rows(b->h_p, b->d_p, 4, 1, b, n_bits, hipMemcpyDeviceToHost, st));
-  if (b->flags & GMX_BATCH_OUTPUTS)
-    HIPCHK(copy_rows(b->h_out, b->d_out, 4, t.m, b, n_bits, hipMemcpyDeviceToHost, st));
-  if (b->flags & GMX_BATCH_LAST_OUTPUTS)
-    HIPCHK(hipMemcpyAsync(b->h_last, b->d_last, (size_t)b->S * t.m * sizeof(float), hipMemcpyDeviceToHost, st));
-  return xfer_end_download(b->x, st);
-}
-
-// The host waits for THIS batch's queued work: its upload, the device work that used it, its
-// download.  (Work on other batches of the group keeps running.)
-extern "C" int gmx_batch_wait(gmx_batch* b) {
-  if (!b || !b->g) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(b->g->device));
-  return xfer_wait(b->x);
-}
+extern "C" int gmx_batch_download(gmx_batch* b, uint64_t n_bits) { return batch_core_transfer(b, n_bits, GMX_COL_DOWN); }
+extern "C" int gmx_batch_wait(gmx_batch* b) { return batch_core_wait(b); }
 
 extern "C" int gmx_batch_fill_synthetic(gmx_batch* b, uint64_t n_bits, uint64_t seed,
                                         uint64_t restart, int ctx_mode, uint32_t ctx_mod,

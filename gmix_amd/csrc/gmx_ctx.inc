@@ -5,17 +5,16 @@
 // and nine IndirectHash objects of predictor.cpp:54-76, :78-185, :210-249.  Compute is gmx_ctx.hip; nothing here falls
 // back to the CPU.
 
-struct gmx_ctx_batch {
+struct gmx_ctx_batch : GmxBatchCore {
   gmx_ctx* cb = nullptr;
-  int S = 0;
-  uint64_t max_bits = 0, max_fires = 0;
+  uint64_t& max_bits = max_rows;
+  uint64_t max_fires = 0;
   unsigned flags = 0;
   uint8_t* d_bits = nullptr;
   uint32_t* d_values = nullptr;   // only with GMX_CTX_BATCH_VALUES
   uint32_t* d_scratch = nullptr;  // [S][max_fires][H]
   uint8_t* h_bits = nullptr;
   uint32_t* h_values = nullptr;
-  GmxXfer x;
 };
 
 struct gmx_ctx {
@@ -28,7 +27,7 @@ struct gmx_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_mark[2] = {};    // a timed run: behind the chain kernel, behind the expand kernel
   float last_ms[3] = {};         // ... and what its three kernels took (gmx_ctx_last_kernel_ms)
-  std::vector<gmx_ctx_batch*> batches;
+  GmxBatchBank bb;               // its batches
   GmxCountList counts;
   // checkpoint: the chunk list (the same for every stream) and its device arrays, lazily
   std::vector<GmxCtxCkptChunk> chunks;
@@ -104,18 +103,7 @@ hipError_t gmx_launch_ctx_ckpt_scatter(const GmxCtxCkptArgs* a, int n_hash, hipS
 
 static void ctx_batch_free(gmx_ctx_batch* b) {
   if (!b) return;
-  if (b->cb) {
-    (void)hipSetDevice(b->cb->device);
-    (void)hipStreamSynchronize(b->cb->stream);
-    auto& v = b->cb->batches;
-    v.erase(std::remove(v.begin(), v.end(), b), v.end());
-  }
-  void* dv[] = {b->d_bits, b->d_values, b->d_scratch};
-  for (void* p : dv)
-    if (p) (void)hipFree(p);
-  if (b->h_bits) (void)hipHostFree(b->h_bits);
-  if (b->h_values) (void)hipHostFree(b->h_values);
-  xfer_free(b->x);
+  batch_core_free(*b);
   delete b;
 }
 
@@ -128,8 +116,7 @@ extern "C" void gmx_ctx_destroy(gmx_ctx* cb) {
   if (cb->stream) (void)hipStreamSynchronize(cb->stream);
   if (cb->routes_d) (void)hipFree(cb->routes_d);
   if (cb->bit_reply) (void)hipHostFree(cb->bit_reply);
-  for (gmx_ctx_batch* b : cb->batches) b->cb = nullptr;  // shells, as for gmx_batch
-  cb->batches.clear();
+  batch_bank_detach_all(cb->bb);  // shells, as for gmx_batch
   void* dv[] = {cb->banks, cb->dev_d, cb->chunks_d, cb->chunk_cnt_d, cb->chunk_base_d, cb->hash_dense_d,
                 cb->hash_cnt_d, cb->hash_off_d};
   for (void* p : dv)
@@ -251,6 +238,7 @@ extern "C" int gmx_ctx_create(gmx_ctx** out, const gmx_ctx_desc* descs, int n_va
     return GMX_ERR_INVALID;
   }
   cb->device = device;
+  batch_bank_init(cb->bb, cb, device, &cb->stream);  // (no transfer streams: see the comment at gmx_ctx::stream)
   cb->S = n_streams;
   cb->outstanding.assign((size_t)n_streams, 0);
   cb->noted.assign((size_t)n_streams, 0);
@@ -312,46 +300,27 @@ extern "C" int gmx_ctx_set_cu_mask(gmx_ctx* cb, const uint32_t* mask, int n_word
 }
 
 // ---- batches -----------------------------------------------------------------------------------
+static int ctx_batch_alloc(gmx_ctx_batch* b, gmx_ctx* cb, uint64_t max_bits) {
+  int rc = batch_core_alloc(*b, &cb->bb, cb->S, max_bits, true);  // (the pinned arrays too: the accessors never allocate)
+  if (rc) return rc;
+  if (cb->dev.h) BCHK(hipMalloc((void**)&b->d_scratch, (size_t)cb->S * b->max_fires * (size_t)cb->dev.h * 4));
+  return GMX_OK;
+}
 extern "C" int gmx_ctx_batch_create(gmx_ctx_batch** out, gmx_ctx* cb, uint64_t max_bits, unsigned flags) {
   if (!out) return GMX_ERR_INVALID;
   *out = nullptr;
   if (!cb || max_bits == 0 || max_bits > (1ull << 30) || (flags & ~GMX_CTX_BATCH_VALUES)) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(cb->device));
   gmx_ctx_batch* b = new (std::nothrow) gmx_ctx_batch();
   if (!b) return GMX_ERR_NOMEM;
-  b->cb = cb;
-  b->S = cb->S;
-  b->max_bits = max_bits;
+  b->back = (void**)&b->cb;
   b->max_fires = max_bits / 8 + 2;  // byte openings of a run: at most (8 + n - 1) / 8 + 1
   b->flags = flags;
-  const size_t R = (size_t)cb->S * max_bits;
-#define BCHK(call)                                           \
-  do {                                                       \
-    hipError_t e_ = (call);                                  \
-    if (e_ != hipSuccess) {                                  \
-      int r_ = hip_fail(e_, #call);                          \
-      ctx_batch_free(b);                                     \
-      return e_ == hipErrorOutOfMemory ? GMX_ERR_NOMEM : r_; \
-    }                                                        \
-  } while (0)
-  BCHK(hipMalloc((void**)&b->d_bits, R));
-  if (flags & GMX_CTX_BATCH_VALUES) BCHK(hipMalloc((void**)&b->d_values, R * (size_t)cb->dev.v * 4));
-  if (cb->dev.h) BCHK(hipMalloc((void**)&b->d_scratch, (size_t)cb->S * b->max_fires * (size_t)cb->dev.h * 4));
-  BCHK(hipHostMalloc((void**)&b->h_bits, R, hipHostMallocDefault));
-  memset(b->h_bits, 0, R);
-  if (flags & GMX_CTX_BATCH_VALUES) {
-    BCHK(hipHostMalloc((void**)&b->h_values, R * (size_t)cb->dev.v * 4, hipHostMallocDefault));
-    memset(b->h_values, 0, R * (size_t)cb->dev.v * 4);
+  gmx_ctx_batch_cols(b->cols, b, cb->dev.v, flags);
+  int rc = ctx_batch_alloc(b, cb, max_bits);
+  if (rc) {
+    ctx_batch_free(b);
+    return rc;
   }
-#undef BCHK
-  {
-    int rcx = xfer_init(b->x);
-    if (rcx) {
-      ctx_batch_free(b);
-      return rcx;
-    }
-  }
-  cb->batches.push_back(b);
   *out = b;
   return GMX_OK;
 }
@@ -360,35 +329,13 @@ extern "C" uint64_t gmx_ctx_batch_max_bits(const gmx_ctx_batch* b) { return b ? 
 extern "C" uint8_t* gmx_ctx_batch_bits(gmx_ctx_batch* b) { return (b && b->cb) ? b->h_bits : nullptr; }
 extern "C" const uint32_t* gmx_ctx_batch_values(gmx_ctx_batch* b) { return (b && b->cb) ? b->h_values : nullptr; }
 
-static hipError_t ctx_copy_rows(void* dst, const void* src, size_t row_bytes, gmx_ctx_batch* b, uint64_t n_bits,
-                                hipMemcpyKind kind, hipStream_t st) {
-  const size_t pitch = (size_t)b->max_bits * row_bytes, width = (size_t)n_bits * row_bytes;
-  if (n_bits == b->max_bits || b->S == 1)
-    return hipMemcpyAsync(dst, src, b->S == 1 ? width : pitch * b->S, kind, st);
-  return hipMemcpy2DAsync(dst, pitch, src, pitch, width, (size_t)b->S, kind, st);
-}
-
-extern "C" int gmx_ctx_batch_upload(gmx_ctx_batch* b, uint64_t n_bits) {
-  if (!b || !b->cb || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  gmx_ctx* cb = b->cb;
-  HIPCHK(hipSetDevice(cb->device));
-  HIPCHK(ctx_copy_rows(b->d_bits, b->h_bits, 1, b, n_bits, hipMemcpyHostToDevice, cb->stream));
-  return xfer_end_upload(b->x, cb->stream, cb->stream);
-}
+// (on the bank's own stream, as for the Match banks)
+extern "C" int gmx_ctx_batch_upload(gmx_ctx_batch* b, uint64_t n_bits) { return batch_core_transfer(b, n_bits, GMX_COL_UP); }
 extern "C" int gmx_ctx_batch_download(gmx_ctx_batch* b, uint64_t n_bits) {
-  if (!b || !b->cb || n_bits > b->max_bits || !b->d_values) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  gmx_ctx* cb = b->cb;
-  HIPCHK(hipSetDevice(cb->device));
-  HIPCHK(ctx_copy_rows(b->h_values, b->d_values, 4 * (size_t)cb->dev.v, b, n_bits, hipMemcpyDeviceToHost, cb->stream));
-  return xfer_end_download(b->x, cb->stream);
+  if (b && !(b->flags & GMX_CTX_BATCH_VALUES)) return GMX_ERR_INVALID;  // (there is nothing to fetch)
+  return batch_core_transfer(b, n_bits, GMX_COL_DOWN);
 }
-extern "C" int gmx_ctx_batch_wait(gmx_ctx_batch* b) {
-  if (!b || !b->cb) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(b->cb->device));
-  return xfer_wait(b->x);
-}
+extern "C" int gmx_ctx_batch_wait(gmx_ctx_batch* b) { return batch_core_wait(b); }
 
 // ---- compute -----------------------------------------------------------------------------------
 static int ctx_route_ok(const gmx_ctx* cb, const int32_t* route, int n, int want) {

@@ -4,10 +4,9 @@
 // predictor.cpp:78-120, :122-185, :210-250) and their IndirectMemory (long-term-memory.h:11-25)
 // for S independent streams.  Compute is gmx_indirect.hip; nothing here falls back to the CPU.
 
-struct gmx_ind_batch {
+struct gmx_ind_batch : GmxBatchCore {
   gmx_indirect* ib = nullptr;
-  int S = 0;
-  uint64_t max_bits = 0;
+  uint64_t& max_bits = max_rows;
   uint32_t* d_ctx = nullptr;
   uint32_t* d_bc = nullptr;
   uint8_t* d_bits = nullptr;
@@ -21,7 +20,6 @@ struct gmx_ind_batch {
   uint8_t* h_bits = nullptr;
   float* h_pred = nullptr;
   uint8_t* h_act = nullptr;
-  GmxXfer x;                     // its transfers against the kernels that use it
 };
 
 struct gmx_indirect {
@@ -35,7 +33,7 @@ struct gmx_indirect {
   hipStream_t up_stream = nullptr, down_stream = nullptr;  // record batches beside the kernels
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<uint32_t> table_size;
-  std::vector<gmx_ind_batch*> batches;
+  GmxBatchBank bb;               // its record batches
   gmx_ind_batch* one = nullptr;  // 1-bit batch of the per-bit surface
   std::vector<uint8_t> fwd_done;
   GmxCountList counts;                          // per-stream bit counts of ragged launches
@@ -139,21 +137,7 @@ hipError_t gmx_launch_indirect_session_ctx(const GmxIndDev* dv, int k_ind, uint8
 
 static void ind_batch_free(gmx_ind_batch* b) {
   if (!b) return;
-  if (b->ib) {
-    (void)hipSetDevice(b->ib->device);
-    (void)hipStreamSynchronize(b->ib->stream);
-    if (b->ib->up_stream) (void)hipStreamSynchronize(b->ib->up_stream);
-    if (b->ib->down_stream) (void)hipStreamSynchronize(b->ib->down_stream);
-    auto& v = b->ib->batches;
-    v.erase(std::remove(v.begin(), v.end(), b), v.end());
-  }
-  void* dv[] = {b->d_ctx, b->d_bc, b->d_bits, b->d_pred, b->d_act, b->d_rng, b->d_recent, b->d_cstate};
-  for (void* p : dv)
-    if (p) (void)hipFree(p);
-  void* hv[] = {b->h_ctx, b->h_bc, b->h_bits, b->h_pred, b->h_act};
-  for (void* p : hv)
-    if (p) (void)hipHostFree(p);
-  xfer_free(b->x);
+  batch_core_free(*b);
   delete b;
 }
 
@@ -169,8 +153,7 @@ extern "C" void gmx_indirect_destroy(gmx_indirect* ib) {
     ib->one = nullptr;
   }
   ind_ckpt_free(ib);
-  for (gmx_ind_batch* b : ib->batches) b->ib = nullptr;  // shells, as for gmx_batch
-  ib->batches.clear();
+  batch_bank_detach_all(ib->bb);  // shells, as for gmx_batch
   if (!ib->banks_in_use_by_dead_kernel) {  // (as gmx_group_destroy: leaked rather than freed under a running kernel)
     if (ib->banks) (void)hipFree(ib->banks);
     if (ib->dev_d) (void)hipFree(ib->dev_d);
@@ -251,6 +234,7 @@ extern "C" int gmx_indirect_create(gmx_indirect** out, const gmx_indirect_desc* 
   gmx_indirect* ib = new (std::nothrow) gmx_indirect();
   if (!ib) return GMX_ERR_NOMEM;
   ib->device = device;
+  batch_bank_init(ib->bb, ib, device, &ib->stream, &ib->up_stream, &ib->down_stream);
   ib->S = n_streams;
   ib->dev = d;
   ib->tab_bytes = tab_bytes;
@@ -301,36 +285,15 @@ extern "C" int gmx_indirect_sync(gmx_indirect* ib) {
 static int ind_batch_alloc(gmx_ind_batch** out, gmx_indirect* ib, uint64_t max_bits) {
   if (!out || !ib || max_bits == 0) return GMX_ERR_INVALID;
   *out = nullptr;
-  HIPCHK(hipSetDevice(ib->device));
   gmx_ind_batch* b = new (std::nothrow) gmx_ind_batch();
   if (!b) return GMX_ERR_NOMEM;
-  b->ib = ib;
-  b->S = ib->S;
-  b->max_bits = max_bits;
-  const size_t R = (size_t)ib->S * max_bits, K = ib->dev.k;
-#define BCHK(call)                                 \
-  do {                                             \
-    hipError_t e_ = (call);                        \
-    if (e_ != hipSuccess) {                        \
-      int r_ = hip_fail(e_, #call);                \
-      ind_batch_free(b);                           \
-      return e_ == hipErrorOutOfMemory ? GMX_ERR_NOMEM : r_; \
-    }                                              \
-  } while (0)
-  BCHK(hipMalloc((void**)&b->d_ctx, R * K * 4));
-  BCHK(hipMalloc((void**)&b->d_bc, R * 4));
-  BCHK(hipMalloc((void**)&b->d_bits, R));
-  BCHK(hipMalloc((void**)&b->d_pred, R * 2 * K * 4));
-  BCHK(hipMalloc((void**)&b->d_act, R * 2 * K));
-#undef BCHK
-  {
-    int rcx = xfer_init(b->x);
-    if (rcx) {
-      ind_batch_free(b);
-      return rcx;
-    }
+  b->back = (void**)&b->ib;
+  gmx_ind_batch_cols(b->cols, b, ib->dev.k);
+  int rc = batch_core_alloc(*b, &ib->bb, ib->S, max_bits, false);
+  if (rc) {
+    ind_batch_free(b);
+    return rc;
   }
-  ib->batches.push_back(b);
   *out = b;
   return GMX_OK;
 }
@@ -343,81 +306,26 @@ extern "C" int gmx_ind_batch_create(gmx_ind_batch** out, gmx_indirect* ib, uint6
 extern "C" void gmx_ind_batch_destroy(gmx_ind_batch* b) { ind_batch_free(b); }
 extern "C" uint64_t gmx_ind_batch_max_bits(const gmx_ind_batch* b) { return b ? b->max_bits : 0; }
 
-template <typename T>
-static T* ind_lazy_host(gmx_ind_batch* b, T** slot, size_t count) {
-  if (!b || !b->ib) return nullptr;
-  if (!*slot) {
-    if (hipSetDevice(b->ib->device) != hipSuccess) return nullptr;
-    void* p = nullptr;
-    if (hipHostMalloc(&p, count * sizeof(T), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    memset(p, 0, count * sizeof(T));
-    *slot = (T*)p;
-  }
-  return *slot;
-}
-#define IND_R(b) ((size_t)(b)->S * (b)->max_bits)
 extern "C" uint32_t* gmx_ind_batch_contexts(gmx_ind_batch* b) {
-  return (b && b->ib) ? ind_lazy_host(b, &b->h_ctx, IND_R(b) * b->ib->dev.k) : nullptr;
+  return b ? (uint32_t*)batch_core_host(*b, &b->h_ctx) : nullptr;
 }
 extern "C" uint32_t* gmx_ind_batch_bit_contexts(gmx_ind_batch* b) {
-  return (b && b->ib) ? ind_lazy_host(b, &b->h_bc, IND_R(b)) : nullptr;
+  return b ? (uint32_t*)batch_core_host(*b, &b->h_bc) : nullptr;
 }
-extern "C" uint8_t* gmx_ind_batch_bits(gmx_ind_batch* b) {
-  return (b && b->ib) ? ind_lazy_host(b, &b->h_bits, IND_R(b)) : nullptr;
-}
+extern "C" uint8_t* gmx_ind_batch_bits(gmx_ind_batch* b) { return b ? (uint8_t*)batch_core_host(*b, &b->h_bits) : nullptr; }
 extern "C" const float* gmx_ind_batch_predictions(gmx_ind_batch* b) {
-  return (b && b->ib) ? ind_lazy_host(b, &b->h_pred, IND_R(b) * 2 * b->ib->dev.k) : nullptr;
+  return b ? (float*)batch_core_host(*b, &b->h_pred) : nullptr;
 }
 extern "C" const uint8_t* gmx_ind_batch_active(gmx_ind_batch* b) {
-  return (b && b->ib) ? ind_lazy_host(b, &b->h_act, IND_R(b) * 2 * b->ib->dev.k) : nullptr;
+  return b ? (uint8_t*)batch_core_host(*b, &b->h_act) : nullptr;
 }
 
-static hipError_t ind_copy_rows(void* dst, const void* src, size_t row_bytes, gmx_ind_batch* b, uint64_t n_bits,
-                                hipMemcpyKind kind, hipStream_t st) {
-  const size_t pitch = (size_t)b->max_bits * row_bytes, width = (size_t)n_bits * row_bytes;
-  if (n_bits == b->max_bits || b->S == 1)
-    return hipMemcpyAsync(dst, src, b->S == 1 ? width : pitch * b->S, kind, st);
-  return hipMemcpy2DAsync(dst, pitch, src, pitch, width, (size_t)b->S, kind, st);
-}
-
-extern "C" int gmx_ind_batch_upload(gmx_ind_batch* b, uint64_t n_bits) {
-  if (!b || !b->ib || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  HIPCHK(hipSetDevice(b->ib->device));
-  if (!gmx_ind_batch_contexts(b) || !gmx_ind_batch_bit_contexts(b) || !gmx_ind_batch_bits(b)) return GMX_ERR_NOMEM;
-  // beside the kernels, on a stream of its own (see gmx_batch_upload)
-  hipStream_t st = nullptr;
-  int rc = xfer_begin_upload(b->x, b->ib->stream, &b->ib->up_stream,
-                             (size_t)b->S * n_bits * (4 * (size_t)b->ib->dev.k + 5), &st);
-  if (rc) return rc;
-  HIPCHK(ind_copy_rows(b->d_ctx, b->h_ctx, 4 * (size_t)b->ib->dev.k, b, n_bits, hipMemcpyHostToDevice, st));
-  HIPCHK(ind_copy_rows(b->d_bc, b->h_bc, 4, b, n_bits, hipMemcpyHostToDevice, st));
-  HIPCHK(ind_copy_rows(b->d_bits, b->h_bits, 1, b, n_bits, hipMemcpyHostToDevice, st));
-  return xfer_end_upload(b->x, b->ib->stream, st);
-}
-
+// beside the kernels, on streams of their own (see gmx_batch_upload)
+extern "C" int gmx_ind_batch_upload(gmx_ind_batch* b, uint64_t n_bits) { return batch_core_transfer(b, n_bits, GMX_COL_UP); }
 extern "C" int gmx_ind_batch_download(gmx_ind_batch* b, uint64_t n_bits) {
-  if (!b || !b->ib || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  HIPCHK(hipSetDevice(b->ib->device));
-  if (!gmx_ind_batch_predictions(b) || !gmx_ind_batch_active(b)) return GMX_ERR_NOMEM;
-  hipStream_t st = nullptr;
-  int rc = xfer_begin_download(b->x, b->ib->stream, &b->ib->down_stream,
-                               (size_t)b->S * n_bits * 10 * (size_t)b->ib->dev.k, &st);
-  if (rc) return rc;
-  HIPCHK(ind_copy_rows(b->h_pred, b->d_pred, 8 * (size_t)b->ib->dev.k, b, n_bits, hipMemcpyDeviceToHost, st));
-  HIPCHK(ind_copy_rows(b->h_act, b->d_act, 2 * (size_t)b->ib->dev.k, b, n_bits, hipMemcpyDeviceToHost, st));
-  return xfer_end_download(b->x, st);
+  return batch_core_transfer(b, n_bits, GMX_COL_DOWN);
 }
-
-extern "C" int gmx_ind_batch_wait(gmx_ind_batch* b) {  // this batch's upload, runs and download
-  if (!b || !b->ib) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(b->ib->device));
-  return xfer_wait(b->x);
-}
+extern "C" int gmx_ind_batch_wait(gmx_ind_batch* b) { return batch_core_wait(b); }  // this batch's upload, runs and download
 
 extern "C" int gmx_ind_batch_fill_synthetic(gmx_ind_batch* b, uint64_t n_bits, uint64_t seed, uint64_t restart,
                                             const uint32_t* ctx_mod) {

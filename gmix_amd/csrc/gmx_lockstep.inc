@@ -228,11 +228,7 @@ extern "C" void gmx_lockstep_destroy(gmx_lockstep* ls) {
     }
     if (!gone) {
       if (ls->g) ls->g->banks_in_use_by_dead_kernel = true;
-      if (ls->b && ls->b->g) {  // the batch stays alive, out of the group's list
-        auto& bv = ls->b->g->batches;
-        bv.erase(std::remove(bv.begin(), bv.end(), ls->b), bv.end());
-        ls->b->g = nullptr;
-      }
+      if (ls->b) batch_core_detach(*ls->b);  // the batch stays alive, out of the group's list
       ls->b = nullptr;
       delete ls;
       return;

@@ -4,10 +4,9 @@
 // 10)) together with its share of LongTermMemory (neuron_layer_weights, lstm_output_layer,
 // long-term-memory.h:55-76) for S independent streams.  Compute is gmx_lstm.hip; no CPU fallback.
 
-struct gmx_lstm_batch {
+struct gmx_lstm_batch : GmxBatchCore {
   gmx_lstm* l = nullptr;
-  int S = 0;
-  uint64_t max_bytes = 0;
+  uint64_t& max_bytes = max_rows;  // (its records are bytes)
   float* d_ppm = nullptr;
   uint8_t* d_bytes = nullptr;
   float* d_pred = nullptr;
@@ -18,7 +17,6 @@ struct gmx_lstm_batch {
   float* h_pred = nullptr;
   uint8_t* h_act = nullptr;
   uint32_t* h_ctx = nullptr;
-  GmxXfer x;                     // its transfers against the kernels that use it
 };
 
 struct gmx_lstm {
@@ -44,7 +42,7 @@ struct gmx_lstm {
   size_t adam_cap = 0;
   unsigned adam_seq = 0;
   GmxCountList counts;                  // per-stream byte counts of ragged launches
-  std::vector<gmx_lstm_batch*> batches;
+  GmxBatchBank bb;                      // its record batches
   gmx_lstm_batch* one = nullptr;        // record arrays of the per-byte surface
   std::vector<uint8_t> fwd_done;
   // The range state LstmModel keeps beside the network (top_/mid_/bot_, lstm-model.h) is the caller's inside a byte.
@@ -129,21 +127,7 @@ static void lstm_layout(GmxLstmDev* d) {
 
 static void lstm_batch_free(gmx_lstm_batch* b) {
   if (!b) return;
-  if (b->l) {
-    (void)hipSetDevice(b->l->device);
-    (void)hipStreamSynchronize(b->l->stream);
-    if (b->l->up_stream) (void)hipStreamSynchronize(b->l->up_stream);
-    if (b->l->down_stream) (void)hipStreamSynchronize(b->l->down_stream);
-    auto& v = b->l->batches;
-    v.erase(std::remove(v.begin(), v.end(), b), v.end());
-  }
-  void* dv[] = {b->d_ppm, b->d_bytes, b->d_pred, b->d_act, b->d_ctx};
-  for (void* p : dv)
-    if (p) (void)hipFree(p);
-  void* hv[] = {b->h_ppm, b->h_bytes, b->h_pred, b->h_act, b->h_ctx};
-  for (void* p : hv)
-    if (p) (void)hipHostFree(p);
-  xfer_free(b->x);
+  batch_core_free(*b);
   delete b;
 }
 
@@ -157,8 +141,7 @@ extern "C" void gmx_lstm_destroy(gmx_lstm* l) {
     lstm_batch_free(l->one);
     l->one = nullptr;
   }
-  for (gmx_lstm_batch* b : l->batches) b->l = nullptr;
-  l->batches.clear();
+  batch_bank_detach_all(l->bb);  // shells, as for gmx_batch
   if (!l->banks_in_use_by_dead_kernel) {  // (as gmx_group_destroy: leaked rather than freed under a running kernel)
     if (l->banks) (void)hipFree(l->banks);
     if (l->dev_d) (void)hipFree(l->dev_d);
@@ -222,6 +205,7 @@ extern "C" int gmx_lstm_create(gmx_lstm** out, int n_streams, int device) {
   gmx_lstm* l = new (std::nothrow) gmx_lstm();
   if (!l) return GMX_ERR_NOMEM;
   l->device = device;
+  batch_bank_init(l->bb, l, device, &l->stream, &l->up_stream, &l->down_stream);
   l->S = n_streams;
   lstm_layout(&l->dev);
   l->bytes_seen.assign(n_streams, 0);
@@ -315,41 +299,15 @@ extern "C" int gmx_lstm_get_weights(gmx_lstm* l, int stream, float* w, float* ou
 static int lstm_batch_alloc(gmx_lstm_batch** out, gmx_lstm* l, int S, uint64_t max_bytes) {
   if (!out || !l || max_bytes == 0) return GMX_ERR_INVALID;
   *out = nullptr;
-  HIPCHK(hipSetDevice(l->device));
   gmx_lstm_batch* b = new (std::nothrow) gmx_lstm_batch();
   if (!b) return GMX_ERR_NOMEM;
-  b->l = l;
-  b->S = S;
-  b->max_bytes = max_bytes;
-  const size_t R = (size_t)S * max_bytes;
-#define BCHK(call)                                 \
-  do {                                             \
-    hipError_t e_ = (call);                        \
-    if (e_ != hipSuccess) {                        \
-      int r_ = hip_fail(e_, #call);                \
-      lstm_batch_free(b);                          \
-      return e_ == hipErrorOutOfMemory ? GMX_ERR_NOMEM : r_; \
-    }                                              \
-  } while (0)
-  BCHK(hipMalloc((void**)&b->d_ppm, R * GMX_L_NI * 4));
-  BCHK(hipMalloc((void**)&b->d_bytes, R));
-  BCHK(hipMalloc((void**)&b->d_pred, R * 8 * 4));
-  BCHK(hipMalloc((void**)&b->d_act, R * 8));
-  BCHK(hipMalloc((void**)&b->d_ctx, R * 4));
-  BCHK(hipHostMalloc((void**)&b->h_ppm, R * GMX_L_NI * 4, hipHostMallocDefault));
-  BCHK(hipHostMalloc((void**)&b->h_bytes, R, hipHostMallocDefault));
-  BCHK(hipHostMalloc((void**)&b->h_pred, R * 8 * 4, hipHostMallocDefault));
-  BCHK(hipHostMalloc((void**)&b->h_act, R * 8, hipHostMallocDefault));
-  BCHK(hipHostMalloc((void**)&b->h_ctx, R * 4, hipHostMallocDefault));
-#undef BCHK
-  {
-    int rcx = xfer_init(b->x);
-    if (rcx) {
-      lstm_batch_free(b);
-      return rcx;
-    }
+  b->back = (void**)&b->l;
+  gmx_lstm_batch_cols(b->cols, b, GMX_L_NI);
+  int rc = batch_core_alloc(*b, &l->bb, S, max_bytes, true);  // (the pinned arrays too: the accessors below never allocate)
+  if (rc) {
+    lstm_batch_free(b);
+    return rc;
   }
-  l->batches.push_back(b);
   *out = b;
   return GMX_OK;
 }
@@ -366,43 +324,14 @@ extern "C" const float* gmx_lstm_batch_predictions(gmx_lstm_batch* b) { return (
 extern "C" const uint8_t* gmx_lstm_batch_active(gmx_lstm_batch* b) { return (b && b->l) ? b->h_act : nullptr; }
 extern "C" const uint32_t* gmx_lstm_batch_contexts(gmx_lstm_batch* b) { return (b && b->l) ? b->h_ctx : nullptr; }
 
-// Copy the first n_bytes records of every stream (rows of a [S][max_bytes][row_bytes] array).
-static hipError_t lstm_copy_rows(void* dst, const void* src, size_t row_bytes, gmx_lstm_batch* b, uint64_t n_bytes,
-                                 hipMemcpyKind kind, hipStream_t st) {
-  const size_t pitch = (size_t)b->max_bytes * row_bytes, width = (size_t)n_bytes * row_bytes;
-  if (n_bytes == b->max_bytes || b->S == 1)
-    return hipMemcpyAsync(dst, src, b->S == 1 ? width : pitch * b->S, kind, st);
-  return hipMemcpy2DAsync(dst, pitch, src, pitch, width, (size_t)b->S, kind, st);
-}
+// beside the kernels, on streams of their own (see gmx_batch_upload)
 extern "C" int gmx_lstm_batch_upload(gmx_lstm_batch* b, uint64_t n_bytes) {
-  if (!b || !b->l || n_bytes > b->max_bytes) return GMX_ERR_INVALID;
-  if (n_bytes == 0) return GMX_OK;
-  HIPCHK(hipSetDevice(b->l->device));
-  // beside the kernels, on a stream of its own (see gmx_batch_upload)
-  hipStream_t st = nullptr;
-  int rc = xfer_begin_upload(b->x, b->l->stream, &b->l->up_stream, (size_t)b->S * n_bytes * (GMX_L_NI * 4 + 1), &st);
-  if (rc) return rc;
-  HIPCHK(lstm_copy_rows(b->d_ppm, b->h_ppm, GMX_L_NI * 4, b, n_bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(lstm_copy_rows(b->d_bytes, b->h_bytes, 1, b, n_bytes, hipMemcpyHostToDevice, st));
-  return xfer_end_upload(b->x, b->l->stream, st);
+  return batch_core_transfer(b, n_bytes, GMX_COL_UP);
 }
 extern "C" int gmx_lstm_batch_download(gmx_lstm_batch* b, uint64_t n_bytes) {
-  if (!b || !b->l || n_bytes > b->max_bytes) return GMX_ERR_INVALID;
-  if (n_bytes == 0) return GMX_OK;
-  HIPCHK(hipSetDevice(b->l->device));
-  hipStream_t st = nullptr;
-  int rc = xfer_begin_download(b->x, b->l->stream, &b->l->down_stream, (size_t)b->S * n_bytes * 44, &st);
-  if (rc) return rc;
-  HIPCHK(lstm_copy_rows(b->h_pred, b->d_pred, 8 * 4, b, n_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(lstm_copy_rows(b->h_act, b->d_act, 8, b, n_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(lstm_copy_rows(b->h_ctx, b->d_ctx, 4, b, n_bytes, hipMemcpyDeviceToHost, st));
-  return xfer_end_download(b->x, st);
+  return batch_core_transfer(b, n_bytes, GMX_COL_DOWN);
 }
-extern "C" int gmx_lstm_batch_wait(gmx_lstm_batch* b) {  // this batch's upload, runs and download
-  if (!b || !b->l) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(b->l->device));
-  return xfer_wait(b->x);
-}
+extern "C" int gmx_lstm_batch_wait(gmx_lstm_batch* b) { return batch_core_wait(b); }  // this batch's upload, runs and download
 
 // The host's share of a launch over bytes [0, n) of streams s0 .. s0 + ns - 1: Adam's scalars (lstm-layer.cpp:15-21,
 // :27-32) of every backward pass the launch will run -- they depend on the step count only and are computed here with

@@ -5,10 +5,9 @@
 // BasicContexts::Learn (basic-contexts.cpp:44-53), for S independent streams.  Compute is gmx_match.hip; nothing
 // here falls back to the CPU.
 
-struct gmx_match_batch {
+struct gmx_match_batch : GmxBatchCore {
   gmx_match* mb = nullptr;
-  int S = 0;
-  uint64_t max_bits = 0;
+  uint64_t& max_bits = max_rows;
   uint32_t* d_ctx = nullptr;
   uint32_t* d_bc = nullptr;
   uint8_t* d_bits = nullptr;
@@ -21,7 +20,6 @@ struct gmx_match_batch {
   float* h_pred = nullptr;
   uint8_t* h_act = nullptr;
   uint32_t* h_long = nullptr;
-  GmxXfer x;
 };
 
 struct gmx_match {
@@ -32,7 +30,7 @@ struct gmx_match {
   uint8_t* hist = nullptr;         // [S][hist_cap]
   hipStream_t stream = nullptr;    // kernels AND record transfers: the bank adds ONE stream to its priority level
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<gmx_match_batch*> batches;
+  GmxBatchBank bb;                 // its record batches
   gmx_match_batch* one = nullptr;  // 1-bit batch of the per-bit surface
   std::vector<uint8_t> fwd_done;   // per-bit protocol: forward seen, learn allowed
   std::vector<uint32_t> fwd_bc;    // bit_context of that forward
@@ -72,19 +70,7 @@ static int stream_with_cu_mask(hipStream_t* st, const uint32_t* mask, int n_word
 
 static void match_batch_free(gmx_match_batch* b) {
   if (!b) return;
-  if (b->mb) {
-    (void)hipSetDevice(b->mb->device);
-    (void)hipStreamSynchronize(b->mb->stream);
-    auto& v = b->mb->batches;
-    v.erase(std::remove(v.begin(), v.end(), b), v.end());
-  }
-  void* dv[] = {b->d_ctx, b->d_bc, b->d_bits, b->d_pred, b->d_act, b->d_long};
-  for (void* p : dv)
-    if (p) (void)hipFree(p);
-  void* hv[] = {b->h_ctx, b->h_bc, b->h_bits, b->h_pred, b->h_act, b->h_long};
-  for (void* p : hv)
-    if (p) (void)hipHostFree(p);
-  xfer_free(b->x);
+  batch_core_free(*b);
   delete b;
 }
 
@@ -99,8 +85,7 @@ extern "C" void gmx_match_destroy(gmx_match* mb) {
     match_batch_free(mb->one);
     mb->one = nullptr;
   }
-  for (gmx_match_batch* b : mb->batches) b->mb = nullptr;  // shells, as for gmx_batch
-  mb->batches.clear();
+  batch_bank_detach_all(mb->bb);  // shells, as for gmx_batch
   void* dv[] = {mb->banks,       mb->hist,          mb->dev_d,       mb->chunks_d, mb->chunk_cnt_d, mb->chunk_base_d,
                 mb->model_cnt_d, mb->model_dense_d, mb->model_off_d};
   for (void* p : dv)
@@ -172,6 +157,7 @@ extern "C" int gmx_match_create(gmx_match** out, const gmx_match_desc* models, i
   gmx_match* mb = new (std::nothrow) gmx_match();
   if (!mb) return GMX_ERR_NOMEM;
   mb->device = device;
+  batch_bank_init(mb->bb, mb, device, &mb->stream);  // (no transfer streams: see gmx_match_batch_upload)
   mb->S = n_streams;
   mb->dev = d;
   mb->fwd_done.assign(n_streams, 0);
@@ -237,37 +223,15 @@ static int match_batch_alloc(gmx_match_batch** out, gmx_match* mb, uint64_t max_
   if (!out) return GMX_ERR_INVALID;
   *out = nullptr;
   if (!mb || max_bits == 0) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(mb->device));
   gmx_match_batch* b = new (std::nothrow) gmx_match_batch();
   if (!b) return GMX_ERR_NOMEM;
-  b->mb = mb;
-  b->S = mb->S;
-  b->max_bits = max_bits;
-  const size_t R = (size_t)mb->S * max_bits, K = mb->dev.k;
-#define BCHK(call)                                 \
-  do {                                             \
-    hipError_t e_ = (call);                        \
-    if (e_ != hipSuccess) {                        \
-      int r_ = hip_fail(e_, #call);                \
-      match_batch_free(b);                         \
-      return e_ == hipErrorOutOfMemory ? GMX_ERR_NOMEM : r_; \
-    }                                              \
-  } while (0)
-  BCHK(hipMalloc((void**)&b->d_ctx, R * K * 4));
-  BCHK(hipMalloc((void**)&b->d_bc, R * 4));
-  BCHK(hipMalloc((void**)&b->d_bits, R));
-  BCHK(hipMalloc((void**)&b->d_pred, R * K * 4));
-  BCHK(hipMalloc((void**)&b->d_act, R * K));
-  BCHK(hipMalloc((void**)&b->d_long, R * 4));
-#undef BCHK
-  {
-    int rcx = xfer_init(b->x);
-    if (rcx) {
-      match_batch_free(b);
-      return rcx;
-    }
+  b->back = (void**)&b->mb;
+  gmx_match_batch_cols(b->cols, b, mb->dev.k);
+  int rc = batch_core_alloc(*b, &mb->bb, mb->S, max_bits, false);
+  if (rc) {
+    match_batch_free(b);
+    return rc;
   }
-  mb->batches.push_back(b);
   *out = b;
   return GMX_OK;
 }
@@ -278,84 +242,34 @@ extern "C" int gmx_match_batch_create(gmx_match_batch** out, gmx_match* mb, uint
 extern "C" void gmx_match_batch_destroy(gmx_match_batch* b) { match_batch_free(b); }
 extern "C" uint64_t gmx_match_batch_max_bits(const gmx_match_batch* b) { return b ? b->max_bits : 0; }
 
-template <typename T>
-static T* match_lazy_host(gmx_match_batch* b, T** slot, size_t count) {
-  if (!b || !b->mb) return nullptr;
-  if (!*slot) {
-    if (hipSetDevice(b->mb->device) != hipSuccess) return nullptr;
-    void* p = nullptr;
-    if (hipHostMalloc(&p, count * sizeof(T), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    memset(p, 0, count * sizeof(T));
-    *slot = (T*)p;
-  }
-  return *slot;
-}
-#define MATCH_R(b) ((size_t)(b)->S * (b)->max_bits)
 extern "C" uint32_t* gmx_match_batch_contexts(gmx_match_batch* b) {
-  return (b && b->mb) ? match_lazy_host(b, &b->h_ctx, MATCH_R(b) * b->mb->dev.k) : nullptr;
+  return b ? (uint32_t*)batch_core_host(*b, &b->h_ctx) : nullptr;
 }
 extern "C" uint32_t* gmx_match_batch_bit_contexts(gmx_match_batch* b) {
-  return (b && b->mb) ? match_lazy_host(b, &b->h_bc, MATCH_R(b)) : nullptr;
+  return b ? (uint32_t*)batch_core_host(*b, &b->h_bc) : nullptr;
 }
 extern "C" uint8_t* gmx_match_batch_bits(gmx_match_batch* b) {
-  return (b && b->mb) ? match_lazy_host(b, &b->h_bits, MATCH_R(b)) : nullptr;
+  return b ? (uint8_t*)batch_core_host(*b, &b->h_bits) : nullptr;
 }
 extern "C" const float* gmx_match_batch_predictions(gmx_match_batch* b) {
-  return (b && b->mb) ? match_lazy_host(b, &b->h_pred, MATCH_R(b) * b->mb->dev.k) : nullptr;
+  return b ? (float*)batch_core_host(*b, &b->h_pred) : nullptr;
 }
 extern "C" const uint8_t* gmx_match_batch_active(gmx_match_batch* b) {
-  return (b && b->mb) ? match_lazy_host(b, &b->h_act, MATCH_R(b) * b->mb->dev.k) : nullptr;
+  return b ? (uint8_t*)batch_core_host(*b, &b->h_act) : nullptr;
 }
 extern "C" const uint32_t* gmx_match_batch_longest(gmx_match_batch* b) {
-  return (b && b->mb) ? match_lazy_host(b, &b->h_long, MATCH_R(b)) : nullptr;
+  return b ? (uint32_t*)batch_core_host(*b, &b->h_long) : nullptr;
 }
 
-static hipError_t match_copy_rows(void* dst, const void* src, size_t row_bytes, gmx_match_batch* b, uint64_t n_bits,
-                                  hipMemcpyKind kind, hipStream_t st) {
-  const size_t pitch = (size_t)b->max_bits * row_bytes, width = (size_t)n_bits * row_bytes;
-  if (n_bits == b->max_bits || b->S == 1)
-    return hipMemcpyAsync(dst, src, b->S == 1 ? width : pitch * b->S, kind, st);
-  return hipMemcpy2DAsync(dst, pitch, src, pitch, width, (size_t)b->S, kind, st);
-}
-
+// On the bank's own stream: the Match bank shares its priority level with the Indirect banks, whose three streams
+// leave one of the level's four hardware queues (see bank_stream_create), and its records are 29 bytes a bit.
 extern "C" int gmx_match_batch_upload(gmx_match_batch* b, uint64_t n_bits) {
-  if (!b || !b->mb || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  gmx_match* mb = b->mb;
-  HIPCHK(hipSetDevice(mb->device));
-  if (!gmx_match_batch_contexts(b) || !gmx_match_batch_bit_contexts(b) || !gmx_match_batch_bits(b))
-    return GMX_ERR_NOMEM;
-  // On the bank's own stream: the Match bank shares its priority level with the Indirect banks, whose three streams
-  // leave one of the level's four hardware queues (see bank_stream_create), and its records are 29 bytes a bit.
-  hipStream_t st = mb->stream;
-  HIPCHK(match_copy_rows(b->d_ctx, b->h_ctx, 4 * (size_t)mb->dev.k, b, n_bits, hipMemcpyHostToDevice, st));
-  HIPCHK(match_copy_rows(b->d_bc, b->h_bc, 4, b, n_bits, hipMemcpyHostToDevice, st));
-  HIPCHK(match_copy_rows(b->d_bits, b->h_bits, 1, b, n_bits, hipMemcpyHostToDevice, st));
-  return xfer_end_upload(b->x, mb->stream, st);
+  return batch_core_transfer(b, n_bits, GMX_COL_UP);
 }
-
 extern "C" int gmx_match_batch_download(gmx_match_batch* b, uint64_t n_bits) {
-  if (!b || !b->mb || n_bits > b->max_bits) return GMX_ERR_INVALID;
-  if (n_bits == 0) return GMX_OK;
-  gmx_match* mb = b->mb;
-  HIPCHK(hipSetDevice(mb->device));
-  if (!gmx_match_batch_predictions(b) || !gmx_match_batch_active(b) || !gmx_match_batch_longest(b))
-    return GMX_ERR_NOMEM;
-  hipStream_t st = mb->stream;  // behind the kernels that wrote the results (see gmx_match_batch_upload)
-  HIPCHK(match_copy_rows(b->h_pred, b->d_pred, 4 * (size_t)mb->dev.k, b, n_bits, hipMemcpyDeviceToHost, st));
-  HIPCHK(match_copy_rows(b->h_act, b->d_act, (size_t)mb->dev.k, b, n_bits, hipMemcpyDeviceToHost, st));
-  HIPCHK(match_copy_rows(b->h_long, b->d_long, 4, b, n_bits, hipMemcpyDeviceToHost, st));
-  return xfer_end_download(b->x, st);
+  return batch_core_transfer(b, n_bits, GMX_COL_DOWN);
 }
-
-extern "C" int gmx_match_batch_wait(gmx_match_batch* b) {
-  if (!b || !b->mb) return GMX_ERR_INVALID;
-  HIPCHK(hipSetDevice(b->mb->device));
-  return xfer_wait(b->x);
-}
+extern "C" int gmx_match_batch_wait(gmx_match_batch* b) { return batch_core_wait(b); }
 
 // ---- capacity --------------------------------------------------------------------------------
 // The true history sizes from the device (the bank's stream is drained first).
@@ -508,7 +422,6 @@ static int match_ensure_one(gmx_match* mb) {
   int rc = match_batch_alloc(&mb->one, mb, 1);
   if (rc) return rc;
   gmx_match_batch* b = mb->one;
-  mb->batches.erase(std::remove(mb->batches.begin(), mb->batches.end(), b), mb->batches.end());
   if (!gmx_match_batch_contexts(b) || !gmx_match_batch_bit_contexts(b) || !gmx_match_batch_bits(b) ||
       !gmx_match_batch_predictions(b) || !gmx_match_batch_active(b) || !gmx_match_batch_longest(b))
     return GMX_ERR_NOMEM;
