@@ -57,9 +57,12 @@
 #include "contexts/basic-contexts.h"  // ... and its BasicContexts, which gmx::GpuBasicContexts forwards to
 
 #include "gmxmix.h"  // include/gmxmix.h
+#include "gmx_sections.h"  // the byte layout of the sparse .long sections the banks stage
 
 namespace gmx {
 
+template <class Bank>
+class DeviceBank;
 class GpuMixer;
 class GpuMixerBank;
 class GpuIndirect;
@@ -216,8 +219,8 @@ class MixerPool {
   }
   // The LSTM's initial gate weights are a constant of the reference: every Predictor constructor begins with
   // srand(0xDEADBEEF) (predictor.cpp:18) and the LSTM is the first model that draws (lstm-layer.h:41; BasicContexts,
-  // the interval contexts and PPMd, built before it, draw nothing).  A pool that hosts many Predictors draws the
-  // 3 x 50 x 563 numbers ONCE, here, from the same rand() while nothing else runs, and gmx::GpuLstmModel's constructor
+  // the interval contexts and PPMd, built before it, draw nothing).  A pool that hosts many Predictors draws
+  // the 3 x 50 x 563 numbers ONCE, here, from the same rand() while nothing else runs, and gmx::GpuLstmModel's constructor
   // takes them from the pool instead of the process-wide generator -- so that Predictors whose LSTM is on the device
   // can be built side by side on many threads (the reference's constructor, 65 ms of host work each, was 4 of the
   // 5 seconds a 64-file run of 30 KB files took: VERDICT r3 #1).  The draw is checked against its known FNV-1a
@@ -325,7 +328,9 @@ class MixerPool {
   int lockstep_streams() const { return ls_participants_; }
 
  private:
-  friend class GpuMixerBank;
+  template <class Bank>
+  friend class DeviceBank;  // attach, detach, the locked calls: what every bank does alike
+  friend class GpuMixerBank;  // ... and the banks for the rings, the lock step and their Ensure*
   friend class GpuIndirectBank;
   friend class GpuLstmModel;
   friend class GpuMatchBank;
@@ -929,20 +934,99 @@ class MixerPool {
   std::vector<uint64_t> n_cur_, n_in_[kRing], n_bytes_;
 };
 
-// All mixers of one Predictor: one stream of a gmx_group (the Predictor's own, or a MixerPool's).
-class GpuMixerBank {
+// What the device banks of one Predictor share: its stream of the pool, the registry that finds a bank by the
+// Predictor's LongTermMemory, the bank's back-pointer in its MixerPool::Stream, and the ways a C-ABI call is made --
+// under the pool's mutex, under two pools' for a copy, twice for an export.  `Bank` names itself for the error texts
+// (kWho) and its back-pointer (kBack); the order of Settle / SyncIfAhead / Unstage / Ensure around a call stays each
+// bank's own, they differ on purpose.
+template <class Bank>
+class DeviceBank {
  public:
-  // The bank of the Predictor that owns `ltm` (created on first use, gone with its last mixer).
-  static std::shared_ptr<GpuMixerBank> For(ShortTermMemory& stm, LongTermMemory& ltm) {
+  // The bank of the Predictor that owns `ltm` (created on first use, gone with its last model).
+  static std::shared_ptr<Bank> For(ShortTermMemory& stm, LongTermMemory& ltm, bool* created = nullptr) {
     std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
     auto& reg = Registry();
     auto it = reg.find(&ltm);
     if (it != reg.end())
       if (auto sp = it->second.lock()) return sp;
-    std::shared_ptr<GpuMixerBank> sp(new GpuMixerBank(stm, ltm));
+    std::shared_ptr<Bank> sp(new Bank(stm, ltm));
     reg[&ltm] = sp;
+    if (created) *created = true;
     return sp;
   }
+  DeviceBank(const DeviceBank&) = delete;
+  DeviceBank& operator=(const DeviceBank&) = delete;
+
+ protected:
+  DeviceBank(ShortTermMemory& stm, LongTermMemory& ltm, Bank* self) : stm_(stm), ltm_(ltm) {  // self: the derived `this`
+    pool_ = MixerPool::Attach(&ltm, &slot_);
+    std::lock_guard<std::mutex> lk(pool_->mu_);
+    st().*Bank::kBack = self;
+  }
+  // The first thing ~Bank() does: the thread that leads a round may look at the back-pointer, so it goes, under mu_,
+  // before any member of the bank does.
+  void Retire() {
+    std::lock_guard<std::mutex> lk(pool_->mu_);
+    st().*Bank::kBack = nullptr;
+  }
+  ~DeviceBank() {
+    pool_->Detach(slot_);
+    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
+    Registry().erase(&ltm_);  // (a bank that is its own model -- the LSTM -- was never entered)
+  }
+  static std::map<const LongTermMemory*, std::weak_ptr<Bank>>& Registry() {
+    static std::map<const LongTermMemory*, std::weak_ptr<Bank>> r;
+    return r;
+  }
+  MixerPool::Stream& st() const { return pool_->streams_[slot_]; }
+  void Check(const char* what, int rc) { pool_->Check(Bank::kWho, what, rc); }
+  // a C-ABI call on the pool's (possibly shared) objects; inlined, it is on the per-bit path
+  template <class F>
+  void Call(const char* what, F f) {
+    pool_->Call(Bank::kWho, what, f);
+  }
+  // A device-to-device copy from a stream of `o`'s pool: the same pool's call, or -- two pools -- both pools' calls held
+  // off, always in address order.
+  template <class F>
+  void CopyLocked(const Bank& o, const char* what, F f) {
+    if (o.pool_ == pool_) return Call(what, f);
+    MixerPool *a = pool_.get(), *b = o.pool_.get();
+    if (b < a) std::swap(a, b);
+    int rc;
+    {
+      std::lock_guard<std::mutex> la(a->mu_);
+      std::lock_guard<std::mutex> lb(b->mu_);
+      rc = f();
+    }
+    Check(what, rc);
+  }
+  // Ask the sizes, allocate, ask again: fetch(long, &n_long, short, &n_short) is the bank's export call (one that has a
+  // single section leaves the other pair alone).  False, and the buffers not cut to size, when the pool has failed.
+  template <class F>
+  bool Export(const char* what, std::vector<char>* l, std::vector<char>* sh, F fetch) {
+    size_t nl = 0, ns = 0;
+    Call(what, [&] { return fetch(nullptr, &nl, nullptr, &ns); });
+    l->assign(nl ? nl : 1, 0);
+    sh->assign(ns ? ns : 1, 0);
+    Call(what, [&] { return fetch(l->data(), &nl, sh->data(), &ns); });
+    if (pool_->status()) return false;
+    l->resize(nl);
+    sh->resize(ns);
+    return true;
+  }
+  // The mixers' bank brings every chunk in flight home (the other models' Copy / WriteToDisk come before the mixers').
+  void SyncIfAhead();
+
+  ShortTermMemory& stm_;
+  LongTermMemory& ltm_;
+  std::shared_ptr<MixerPool> pool_;
+  int slot_ = 0;
+  bool import_pending_ = false;
+};
+
+// All mixers of one Predictor: one stream of a gmx_group (the Predictor's own, or a MixerPool's).
+class GpuMixerBank : public DeviceBank<GpuMixerBank> {
+ public:
   // The bank of the Predictor object at [p, p + size): its LongTermMemory is a member of it (predictor.h:41).
   static std::shared_ptr<GpuMixerBank> Of(const void* p, size_t size) {
     std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
@@ -957,16 +1041,8 @@ class GpuMixerBank {
   ~GpuMixerBank() {
     if (st().ra) pool_->Leave(slot_);
     if (st().ls) pool_->LeaveLockstep(slot_);
-    {
-      std::lock_guard<std::mutex> lk(pool_->mu_);
-      st().mixers = nullptr;
-    }
-    pool_->Detach(slot_);
-    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
-    Registry().erase(&ltm_);
+    Retire();
   }
-  GpuMixerBank(const GpuMixerBank&) = delete;
-  GpuMixerBank& operator=(const GpuMixerBank&) = delete;
 
   gmx_group* group() { return group_; }
   int stream() const { return slot_; }
@@ -1036,22 +1112,11 @@ class GpuMixerBank {
   friend class GpuLstmModel;
   friend class GpuMatchBank;
   friend class GpuCtxBank;
+  friend class DeviceBank<GpuMixerBank>;
+  static constexpr const char* kWho = "gmx::GpuMixer";
+  static constexpr auto kBack = &MixerPool::Stream::mixers;
   const unsigned int* MixerContextAddress(size_t j) const;
-  GpuMixerBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
-    pool_ = MixerPool::Attach(&ltm, &slot_);
-    std::lock_guard<std::mutex> lk(pool_->mu_);
-    st().mixers = this;
-  }
-  static std::map<const LongTermMemory*, std::weak_ptr<GpuMixerBank>>& Registry() {
-    static std::map<const LongTermMemory*, std::weak_ptr<GpuMixerBank>> r;
-    return r;
-  }
-  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
-  void Check(const char* what, int rc) { pool_->Check("gmx::GpuMixer", what, rc); }
-  template <class F>
-  void Call(const char* what, F f) {
-    pool_->Call("gmx::GpuMixer", what, f);
-  }
+  GpuMixerBank(ShortTermMemory& stm, LongTermMemory& ltm) : DeviceBank(stm, ltm, this) {}
   int Register(GpuMixer* m, int layer, unsigned table_size, float lr, int memory_index, int weight_size) {
     gmx_mixer_desc d;
     d.layer = layer;
@@ -1093,27 +1158,14 @@ class GpuMixerBank {
     if (st().ra) SyncRunAhead();
     import_pending_ = false;
     std::vector<char> buf;
-    auto put = [&buf](const void* p, size_t n) {
-      const char* c = static_cast<const char*>(p);
-      buf.insert(buf.end(), c, c + n);
-    };
-    for (size_t j = 0; j < descs_.size(); ++j) {  // the layout of long-term-memory.cpp:35-54
+    for (size_t j = 0; j < descs_.size(); ++j) {
       auto& table = ltm_.mixers[memory_index_[j]].mixer_table;
-      uint32_t n = 0, input_size = 0;
-      for (auto& row : table)
-        if (row) {
-          ++n;
-          input_size = (uint32_t)row->weights.size();
-        }
-      put(&n, 4);
-      put(&input_size, 4);
-      for (uint32_t c = 0; c < table.size(); ++c) {
-        if (!table[c]) continue;
-        uint64_t steps = table[c]->steps;
-        put(&c, 4);
-        put(&steps, 8);
-        put(&table[c]->weights[0], 4 * table[c]->weights.size());
-      }
+      sections::MixerEncode(sections::Sink{buf}, (uint32_t)table.size(), [&](uint32_t c, uint64_t* steps, uint32_t* n) {
+        if (!table[c]) return (const float*)nullptr;
+        *steps = table[c]->steps;
+        *n = (uint32_t)table[c]->weights.size();
+        return (const float*)&table[c]->weights[0];
+      });
     }
     Call("gmx_bank_import",
          [&] { return gmx_bank_import(group_, slot_, buf.data(), buf.size(), short_in_.data(), short_in_.size()); });
@@ -1124,32 +1176,25 @@ class GpuMixerBank {
   void Stage() {
     Settle();
     if (st().ra) SyncRunAhead();
-    size_t nl = 0, ns = 0;
-    Call("gmx_bank_export", [&] { return gmx_bank_export(group_, slot_, nullptr, &nl, nullptr, &ns); });
-    std::vector<char> l(nl ? nl : 1);
-    short_cache_.assign(ns ? ns : 1, 0);
-    Call("gmx_bank_export", [&] { return gmx_bank_export(group_, slot_, l.data(), &nl, short_cache_.data(), &ns); });
-    if (status()) return;
-    short_cache_.resize(ns);
-    const char* p = l.data();
-    for (size_t j = 0; j < descs_.size(); ++j) {
+    std::vector<char> l;
+    if (!Export("gmx_bank_export", &l, &short_cache_, [&](char* pl, size_t* nl, char* ps, size_t* ns) {
+          return gmx_bank_export(group_, slot_, pl, nl, ps, ns);
+        }))
+      return;
+    sections::Source src(l.data(), l.size());
+    bool ok = true;
+    for (size_t j = 0; ok && j < descs_.size(); ++j) {
       auto& table = ltm_.mixers[memory_index_[j]].mixer_table;
       table.clear();  // (rows of an earlier staging go; the vector is sized for the reference's writers)
       table.resize(descs_[j].table_size);
-      uint32_t n, input_size;
-      memcpy(&n, p, 4);
-      memcpy(&input_size, p + 4, 4);
-      p += 8;
-      for (uint32_t i = 0; i < n; ++i) {
-        uint32_t c;
-        memcpy(&c, p, 4);
+      ok = sections::MixerDecode(src, descs_[j].table_size, [&](uint32_t c, uint64_t steps, const char* w, uint32_t input_size) {
         MixerData* row = new MixerData(input_size);
-        memcpy(&row->steps, p + 4, 8);
-        memcpy(&row->weights[0], p + 12, 4 * (size_t)input_size);
+        row->steps = steps;
+        memcpy(&row->weights[0], w, 4 * (size_t)input_size);
         table[c].reset(row);
-        p += 12 + 4 * (size_t)input_size;
-      }
+      });
     }
+    if (!ok) Check("gmx_bank_export", GMX_ERR_FORMAT);
     staged_ = true;
   }
   // The staged rows are only for the serialisers: give the host memory back once the stream moves on.
@@ -1231,19 +1276,7 @@ class GpuMixerBank {
     Ensure();
     import_pending_ = false;  // whatever LongTermMemory::Copy moves into the staging area is not ours to import
     ever_ran_ = true;
-    if (o.pool_ == pool_) {
-      Call("gmx_bank_copy", [&] { return gmx_bank_copy(group_, slot_, o.group_, o.slot_); });
-    } else {  // two groups: both pools' calls held off, always in address order
-      MixerPool* a = pool_.get() < o.pool_.get() ? pool_.get() : o.pool_.get();
-      MixerPool* b = pool_.get() < o.pool_.get() ? o.pool_.get() : pool_.get();
-      int rc;
-      {
-        std::lock_guard<std::mutex> la(a->mu_);
-        std::lock_guard<std::mutex> lb(b->mu_);
-        rc = gmx_bank_copy(group_, slot_, o.group_, o.slot_);
-      }
-      Check("gmx_bank_copy", rc);
-    }
+    CopyLocked(o, "gmx_bank_copy", [&] { return gmx_bank_copy(group_, slot_, o.group_, o.slot_); });
     if (st().ra && !o.seen_.empty()) {  // the copied bank's rows are this bank's now
       seen_ = o.seen_;
       seen_count_ = o.seen_count_;
@@ -1262,10 +1295,6 @@ class GpuMixerBank {
   // One round of the ring: the chunk recorded so far goes to the device, the chunk before it comes back.
   int Flush();
 
-  ShortTermMemory& stm_;
-  LongTermMemory& ltm_;
-  std::shared_ptr<MixerPool> pool_;
-  int slot_ = 0;
   gmx_group* group_ = nullptr;
   std::vector<gmx_mixer_desc> descs_;
   std::vector<GpuMixer*> mixers_;
@@ -1275,7 +1304,7 @@ class GpuMixerBank {
   std::vector<float> chain_pred_;
   std::vector<uint8_t> chain_act_;
   std::vector<char> short_cache_, short_in_;
-  bool import_pending_ = false, staged_ = false, ever_ran_ = false;
+  bool staged_ = false, ever_ran_ = false;
   bool ls_predicted_ = false;  // lock step: a Predict waits for its Learn
   // run-ahead
   bool recorded_ = false;
@@ -1290,6 +1319,12 @@ class GpuMixerBank {
   bool track_seen_ = false, first_mark_ = true;
   std::vector<uint64_t> seen_count_;
 };
+
+template <class Bank>
+void DeviceBank<Bank>::SyncIfAhead() {
+  MixerPool::Stream& s = st();
+  if (s.ra && s.mixers) s.mixers->SyncRunAhead();
+}
 
 class GpuMixer : public Model {
  public:
@@ -1365,48 +1400,18 @@ class GpuMixer : public Model {
 // mixers is an Indirect model (predictor.cpp:24-28), so per bit its bank does not run at its own Predict but
 // hands contexts to the first mixer's: gmx_chain_forward then takes both banks through ONE host round trip (the
 // Indirect wave rings the mixers' wave itself).  GMX_CHAIN_FUSED=0 switches back to one call per bank.
-class GpuIndirectBank {
+class GpuIndirectBank : public DeviceBank<GpuIndirectBank> {
  public:
-  static std::shared_ptr<GpuIndirectBank> For(ShortTermMemory& stm, LongTermMemory& ltm) {
-    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
-    auto& reg = Registry();
-    auto it = reg.find(&ltm);
-    if (it != reg.end())
-      if (auto sp = it->second.lock()) return sp;
-    std::shared_ptr<GpuIndirectBank> sp(new GpuIndirectBank(stm, ltm));
-    reg[&ltm] = sp;
-    return sp;
-  }
-  ~GpuIndirectBank() {
-    {
-      std::lock_guard<std::mutex> lk(pool_->mu_);
-      st().indirect = nullptr;
-    }
-    pool_->Detach(slot_);
-    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
-    Registry().erase(&ltm_);
-  }
-  GpuIndirectBank(const GpuIndirectBank&) = delete;
-  GpuIndirectBank& operator=(const GpuIndirectBank&) = delete;
+  ~GpuIndirectBank() { Retire(); }
 
  private:
   friend class GpuIndirect;
   friend class GpuMixerBank;
   friend class GpuCtxBank;
-  GpuIndirectBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
-    pool_ = MixerPool::Attach(&ltm, &slot_);
-    std::lock_guard<std::mutex> lk(pool_->mu_);
-    st().indirect = this;
-  }
-  static std::map<const LongTermMemory*, std::weak_ptr<GpuIndirectBank>>& Registry() {
-    static std::map<const LongTermMemory*, std::weak_ptr<GpuIndirectBank>> r;
-    return r;
-  }
-  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
-  template <class F>
-  void Call(const char* what, F f) {
-    pool_->Call("gmx::GpuIndirect", what, f);
-  }
+  friend class DeviceBank<GpuIndirectBank>;
+  static constexpr const char* kWho = "gmx::GpuIndirect";
+  static constexpr auto kBack = &MixerPool::Stream::indirect;
+  GpuIndirectBank(ShortTermMemory& stm, LongTermMemory& ltm) : DeviceBank(stm, ltm, this) {}
   int Register(GpuIndirect* m, unsigned table_size, float lr, int slot_a, int slot_b, int memory_index) {
     gmx_indirect_desc d;
     d.table_size = table_size;
@@ -1440,7 +1445,7 @@ class GpuIndirectBank {
     for (size_t i = 0; i < descs_.size(); ++i) {
       auto& mem = ltm_.indirect[memory_index_[i]];
       if (on) {
-        const size_t size = (size_t)descs_[i].table_size * 256 + 1;  // indirect.cpp:14-19
+        const size_t size = (size_t)sections::IndirectSize(descs_[i].table_size);
         mem.nonstationary_table.assign(size, 255);
         mem.run_map_table.assign(size, 0);
       } else {
@@ -1457,66 +1462,27 @@ class GpuIndirectBank {
     if (!import_pending_) return;
     import_pending_ = false;
     std::vector<char> buf;
-    auto put = [&buf](const void* p, size_t n) {
-      const char* c = static_cast<const char*>(p);
-      buf.insert(buf.end(), c, c + n);
-    };
-    for (size_t i = 0; i < descs_.size(); ++i) {
-      auto& mem = ltm_.indirect[memory_index_[i]];
-      std::vector<unsigned int> keys;
-      for (unsigned int k = 0; k < mem.nonstationary_table.size(); ++k)
-        if (mem.nonstationary_table[k] != 255) keys.push_back(k);
-      unsigned int size = (unsigned int)keys.size();
-      put(&size, 4);
-      if (size < mem.nonstationary_table.size() / 3) {
-        for (unsigned int key : keys) {
-          put(&key, 4);
-          put(&mem.nonstationary_table[key], 1);
-          put(&mem.run_map_table[key], 1);
-        }
-      } else {
-        put(mem.nonstationary_table.data(), mem.nonstationary_table.size());
-        put(mem.run_map_table.data(), mem.run_map_table.size());
-      }
-      put(mem.nonstationary_predictions.data(), 256 * 4);
-      put(mem.run_map_predictions.data(), 256 * 4);
-    }
+    for (size_t i = 0; i < descs_.size(); ++i) sections::IndirectEncode(sections::Sink{buf}, View(i));
     Call("gmx_indirect_import", [&] { return gmx_indirect_import(h_, slot_, buf.data(), buf.size()); });
     StagingTables(false);
   }
   // Device -> LongTermMemory::indirect, for the reference's writer.
   void Stage() {
     Settle();
-    size_t n = 0;
-    Call("gmx_indirect_export", [&] { return gmx_indirect_export(h_, slot_, nullptr, &n); });
-    std::vector<char> buf(n ? n : 1);
-    Call("gmx_indirect_export", [&] { return gmx_indirect_export(h_, slot_, buf.data(), &n); });
-    if (pool_->status()) return;
+    std::vector<char> buf, none;
+    if (!Export("gmx_indirect_export", &buf, &none,
+                [&](char* p, size_t* n, char*, size_t*) { return gmx_indirect_export(h_, slot_, p, n); }))
+      return;
     StagingTables(true);
-    const char* p = buf.data();
-    for (size_t i = 0; i < descs_.size(); ++i) {
-      auto& mem = ltm_.indirect[memory_index_[i]];
-      const size_t size = mem.nonstationary_table.size();
-      unsigned int count;
-      memcpy(&count, p, 4);
-      p += 4;
-      if (count < size / 3) {
-        for (unsigned int k = 0; k < count; ++k) {
-          unsigned int key;
-          memcpy(&key, p, 4);
-          mem.nonstationary_table[key] = (unsigned char)p[4];
-          mem.run_map_table[key] = (unsigned char)p[5];
-          p += 6;
-        }
-      } else {
-        memcpy(mem.nonstationary_table.data(), p, size);
-        memcpy(mem.run_map_table.data(), p + size, size);
-        p += 2 * size;
-      }
-      memcpy(mem.nonstationary_predictions.data(), p, 256 * 4);
-      memcpy(mem.run_map_predictions.data(), p + 1024, 256 * 4);
-      p += 2048;
-    }
+    sections::Source src(buf.data(), buf.size());
+    bool ok = true;
+    for (size_t i = 0; ok && i < descs_.size(); ++i) ok = sections::IndirectDecode(src, View(i));
+    if (!ok) Check("gmx_indirect_export", GMX_ERR_FORMAT);
+  }
+  sections::IndirectView View(size_t i) {  // model i's staging tables
+    auto& mem = ltm_.indirect[memory_index_[i]];
+    return {mem.nonstationary_table.data(), mem.run_map_table.data(), mem.nonstationary_table.size(),
+            mem.nonstationary_predictions.data(), mem.run_map_predictions.data()};
   }
   void Unstage() {
     if (tables_staged_ && !import_pending_) StagingTables(false);
@@ -1559,10 +1525,6 @@ class GpuIndirectBank {
   }
   void CopyFrom(GpuIndirectBank& o);
 
-  ShortTermMemory& stm_;
-  LongTermMemory& ltm_;
-  std::shared_ptr<MixerPool> pool_;
-  int slot_ = 0;
   gmx_indirect* h_ = nullptr;
   std::vector<gmx_indirect_desc> descs_;
   std::vector<GpuIndirect*> models_;
@@ -1570,7 +1532,7 @@ class GpuIndirectBank {
   std::vector<uint32_t> contexts_;
   std::vector<float> pred_;
   std::vector<uint8_t> active_;
-  bool import_pending_ = false, tables_staged_ = false;
+  bool tables_staged_ = false;
   bool pending_ = false;  // this bit's Predict waits for the mixers' (gmx_chain_forward)
   uint32_t pending_bit_context_ = 0;
 };
@@ -1633,19 +1595,7 @@ inline void GpuIndirectBank::CopyFrom(GpuIndirectBank& o) {
   o.Settle();
   Ensure();
   import_pending_ = false;
-  if (o.pool_ == pool_) {
-    Call("gmx_indirect_copy", [&] { return gmx_indirect_copy(h_, slot_, o.h_, o.slot_); });
-  } else {
-    MixerPool* a = pool_.get() < o.pool_.get() ? pool_.get() : o.pool_.get();
-    MixerPool* b = pool_.get() < o.pool_.get() ? o.pool_.get() : pool_.get();
-    int rc;
-    {
-      std::lock_guard<std::mutex> la(a->mu_);
-      std::lock_guard<std::mutex> lb(b->mu_);
-      rc = gmx_indirect_copy(h_, slot_, o.h_, o.slot_);
-    }
-    pool_->Check("gmx::GpuIndirect", "gmx_indirect_copy", rc);
-  }
+  CopyLocked(o, "gmx_indirect_copy", [&] { return gmx_indirect_copy(h_, slot_, o.h_, o.slot_); });
 }
 
 inline void GpuIndirectBank::PredictAll(ShortTermMemory& stm) {
@@ -1716,12 +1666,12 @@ inline void GpuIndirectBank::ToBlackboard(ShortTermMemory& stm) {
 // network once per byte through gmx_lstm_forward / gmx_lstm_perceive, the bit-level range coding of
 // the byte distribution (lstm-model.cpp:34-48) on the host as in the reference -- or, running ahead, all of it in
 // gmx_lstm_run on the bytes' recorded PPM distributions.
-class GpuLstmModel : public Model {
+class GpuLstmModel : public Model, public DeviceBank<GpuLstmModel> {
  public:
   static constexpr int kCells = 50, kInputs = 563, kHorizon = 100, kOut = 256, kHidden = 51;
   // models/lstm-model.h:11-12
   GpuLstmModel(ShortTermMemory& short_term_memory, LongTermMemory& long_term_memory, bool enable_analysis)
-      : stm_(short_term_memory), ltm_(long_term_memory), top_(255), mid_(127), bot_(0), probs_(1.0 / 256, 256) {
+      : DeviceBank(short_term_memory, long_term_memory, this), top_(255), mid_(127), bot_(0), probs_(1.0 / 256, 256) {
     // What the constructors behind Lstm(256, 256, 50, 1, 100, 0.03, 10, ltm) do to LongTermMemory
     // (lstm.cpp:26-29, lstm-layer.cpp:57-59, :179-194): the output-layer ring, three gate matrices,
     // their initial values drawn from rand() in the reference's interleaved order.
@@ -1749,17 +1699,8 @@ class GpuLstmModel : public Model {
     }
     prediction_index_ = short_term_memory.AddPrediction("LSTM", enable_analysis, this);
     short_term_memory.models_with_skip_connection.push_back(prediction_index_);
-    pool_ = MixerPool::Attach(&long_term_memory, &slot_);
-    std::lock_guard<std::mutex> lk(pool_->mu_);
-    st().lstm = this;
   }
-  ~GpuLstmModel() override {
-    {
-      std::lock_guard<std::mutex> lk(pool_->mu_);
-      st().lstm = nullptr;
-    }
-    pool_->Detach(slot_);
-  }
+  ~GpuLstmModel() override { Retire(); }
   void Predict(ShortTermMemory& short_term_memory, const LongTermMemory&) override {  // lstm-model.cpp:17-49
     MixerPool::Stream& s = st();
     if (s.ls) {  // lock step: the PPM byte distribution of a byte that opens; the device walks the bits itself
@@ -1813,18 +1754,18 @@ class GpuLstmModel : public Model {
   void WriteToDisk(std::ofstream* s) override {
     Settle();
     SyncIfAhead();
-    size_t nl = 0, ns = 0;
-    Call("gmx_lstm_export", [&] { return gmx_lstm_export(h_, slot_, nullptr, &nl, nullptr, &ns); });
-    std::vector<char> l(nl ? nl : 1), sh(ns ? ns : 1);
-    Call("gmx_lstm_export", [&] { return gmx_lstm_export(h_, slot_, l.data(), &nl, sh.data(), &ns); });
-    if (pool_->status()) return;
+    std::vector<char> l, sh;
+    if (!Export("gmx_lstm_export", &l, &sh, [&](char* pl, size_t* nl, char* ps, size_t* ns) {
+          return gmx_lstm_export(h_, slot_, pl, nl, ps, ns);
+        }))
+      return;
     if (!range_on_device_) {  // (after a stretch of run-ahead the device's own copy of these is the current one)
       memcpy(sh.data(), &top_, 4);
       memcpy(sh.data() + 4, &mid_, 4);
       memcpy(sh.data() + 8, &bot_, 4);
       memcpy(sh.data() + 12, &probs_[0], 1024);
     }
-    s->write(sh.data(), ns);
+    s->write(sh.data(), sh.size());
     const float* f = reinterpret_cast<const float*>(l.data());
     for (auto& x : ltm_.lstm_output_layer)
       for (auto& y : x) {
@@ -1860,19 +1801,7 @@ class GpuLstmModel : public Model {
     Ensure();
     SyncIfAhead();
     import_pending_ = false;
-    if (orig->pool_ == pool_) {
-      Call("gmx_lstm_copy", [&] { return gmx_lstm_copy(h_, slot_, orig->h_, orig->slot_); });
-    } else {
-      MixerPool* a = pool_.get() < orig->pool_.get() ? pool_.get() : orig->pool_.get();
-      MixerPool* b = pool_.get() < orig->pool_.get() ? orig->pool_.get() : pool_.get();
-      int rc;
-      {
-        std::lock_guard<std::mutex> la(a->mu_);
-        std::lock_guard<std::mutex> lb(b->mu_);
-        rc = gmx_lstm_copy(h_, slot_, orig->h_, orig->slot_);
-      }
-      pool_->Check("gmx::GpuLstmModel", "gmx_lstm_copy", rc);
-    }
+    CopyLocked(*orig, "gmx_lstm_copy", [&] { return gmx_lstm_copy(h_, slot_, orig->h_, orig->slot_); });
     top_ = orig->top_;
     mid_ = orig->mid_;
     bot_ = orig->bot_;
@@ -1889,12 +1818,9 @@ class GpuLstmModel : public Model {
 
  private:
   friend class GpuMixerBank;
-  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
-  template <class F>
-  void Call(const char* what, F f) {
-    pool_->Call("gmx::GpuLstmModel", what, f);
-  }
-  void SyncIfAhead();
+  friend class DeviceBank<GpuLstmModel>;
+  static constexpr const char* kWho = "gmx::GpuLstmModel";
+  static constexpr auto kBack = &MixerPool::Stream::lstm;
   std::vector<char> LongBytes() const {  // the LSTM section as LongTermMemory writes it
     std::vector<char> l;
     auto put = [&l](const std::valarray<float>& y) {
@@ -1927,16 +1853,11 @@ class GpuLstmModel : public Model {
          [&] { return gmx_lstm_import(h_, slot_, l.data(), l.size(), short_in_.data(), short_in_.size()); });
   }
 
-  ShortTermMemory& stm_;
-  LongTermMemory& ltm_;
-  std::shared_ptr<MixerPool> pool_;
-  int slot_ = 0;
   gmx_lstm* h_ = nullptr;
   int first_layer_ = 0;
   int top_, mid_, bot_, prediction_index_;
   std::valarray<float> probs_;
   std::vector<char> short_in_;
-  bool import_pending_ = false;
   bool range_on_device_ = false;  // top_/mid_/bot_/probs_ were last advanced by the device (run-ahead)
 };
 
@@ -1954,48 +1875,18 @@ class GpuLstmModel : public Model {
 // gmx_batched.h takes the analysis column from the returned longest_match) and gives it the device's size again,
 // not its bytes, when the stream comes home.
 // ================================================================================================
-class GpuMatchBank {
+class GpuMatchBank : public DeviceBank<GpuMatchBank> {
  public:
-  static std::shared_ptr<GpuMatchBank> For(ShortTermMemory& stm, LongTermMemory& ltm) {
-    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
-    auto& reg = Registry();
-    auto it = reg.find(&ltm);
-    if (it != reg.end())
-      if (auto sp = it->second.lock()) return sp;
-    std::shared_ptr<GpuMatchBank> sp(new GpuMatchBank(stm, ltm));
-    reg[&ltm] = sp;
-    return sp;
-  }
-  ~GpuMatchBank() {
-    {
-      std::lock_guard<std::mutex> lk(pool_->mu_);
-      st().match = nullptr;
-    }
-    pool_->Detach(slot_);
-    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
-    Registry().erase(&ltm_);
-  }
-  GpuMatchBank(const GpuMatchBank&) = delete;
-  GpuMatchBank& operator=(const GpuMatchBank&) = delete;
+  ~GpuMatchBank() { Retire(); }
 
  private:
   friend class GpuMatch;
   friend class GpuMixerBank;
   friend class GpuCtxBank;
-  GpuMatchBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
-    pool_ = MixerPool::Attach(&ltm, &slot_);
-    std::lock_guard<std::mutex> lk(pool_->mu_);
-    st().match = this;
-  }
-  static std::map<const LongTermMemory*, std::weak_ptr<GpuMatchBank>>& Registry() {
-    static std::map<const LongTermMemory*, std::weak_ptr<GpuMatchBank>> r;
-    return r;
-  }
-  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
-  template <class F>
-  void Call(const char* what, F f) {
-    pool_->Call("gmx::GpuMatch", what, f);
-  }
+  friend class DeviceBank<GpuMatchBank>;
+  static constexpr const char* kWho = "gmx::GpuMatch";
+  static constexpr auto kBack = &MixerPool::Stream::match;
+  GpuMatchBank(ShortTermMemory& stm, LongTermMemory& ltm) : DeviceBank(stm, ltm, this) {}
   int Register(GpuMatch* m, unsigned table_size, int limit, int slot, int memory_index) {
     gmx_match_desc d;
     d.table_size = table_size;
@@ -2029,8 +1920,10 @@ class GpuMatchBank {
         std::vector<std::array<unsigned char, 5>>().swap(table);
     }
   }
-  // The mixers' bank brings every chunk in flight home (the Match models' Copy / WriteToDisk come before the mixers').
-  void SyncIfAhead();
+  sections::MatchView View(size_t i) {  // model i's staging table
+    auto& mem = ltm_.match_memory[memory_index_[i]];
+    return {mem.table.empty() ? nullptr : mem.table[0].data(), mem.table.size(), mem.predictions.data(), mem.counts.data()};
+  }
   // What LongTermMemory::ReadFromDisk has read since ReadFromDisk was called on the models goes to the device, in the
   // section's own format (long-term-memory.cpp:70-106); the blackboard's slots and new_bit follow (they are
   // ShortTermMemory's, restored by then).
@@ -2040,33 +1933,8 @@ class GpuMatchBank {
     SyncIfAhead();
     import_pending_ = false;
     std::vector<char> buf;
-    auto put = [&buf](const void* p, size_t n) {
-      const char* c = static_cast<const char*>(p);
-      buf.insert(buf.end(), c, c + n);
-    };
-    const unsigned long long hs = ltm_.history.size();
-    put(&hs, 8);
-    put(ltm_.history.data(), ltm_.history.size());
-    for (size_t i = 0; i < descs_.size(); ++i) {
-      auto& mem = ltm_.match_memory[memory_index_[i]];
-      std::vector<unsigned int> keys;
-      for (unsigned int k = 0; k < mem.table.size(); ++k) {
-        const auto& e = mem.table[k];
-        if (e[0] || e[1] || e[2] || e[3] || e[4]) keys.push_back(k);
-      }
-      unsigned int size = (unsigned int)keys.size();
-      put(&size, 4);
-      if (size < (5.0 / 9.0) * mem.table.size()) {
-        for (unsigned int key : keys) {
-          put(&key, 4);
-          put(mem.table[key].data(), 5);
-        }
-      } else {
-        put(mem.table.data(), 5 * mem.table.size());
-      }
-      put(mem.predictions.data(), 256 * 4);
-      put(mem.counts.data(), 256 * 4);
-    }
+    sections::MatchHistoryEncode(sections::Sink{buf}, ltm_.history.data(), ltm_.history.size());
+    for (size_t i = 0; i < descs_.size(); ++i) sections::MatchEncode(sections::Sink{buf}, View(i));
     Call("gmx_match_import", [&] {
       return gmx_match_import(h_, slot_, buf.data(), buf.size(), short_in_.data(), short_in_.size());
     });
@@ -2078,40 +1946,19 @@ class GpuMatchBank {
   void Stage() {
     Settle();
     SyncIfAhead();
-    size_t nl = 0, ns = 0;
-    Call("gmx_match_export", [&] { return gmx_match_export(h_, slot_, nullptr, &nl, nullptr, &ns); });
-    std::vector<char> l(nl ? nl : 1);
-    short_cache_.assign(ns ? ns : 1, 0);
-    Call("gmx_match_export", [&] { return gmx_match_export(h_, slot_, l.data(), &nl, short_cache_.data(), &ns); });
-    if (pool_->status()) return;
-    short_cache_.resize(ns);
+    std::vector<char> l;
+    if (!Export("gmx_match_export", &l, &short_cache_, [&](char* pl, size_t* nl, char* ps, size_t* ns) {
+          return gmx_match_export(h_, slot_, pl, nl, ps, ns);
+        }))
+      return;
     HostTables(true);
-    const char* p = l.data();
-    unsigned long long hs;
-    memcpy(&hs, p, 8);
-    p += 8;
-    ltm_.history.assign(reinterpret_cast<const unsigned char*>(p), reinterpret_cast<const unsigned char*>(p) + hs);
-    p += hs;
-    for (size_t i = 0; i < descs_.size(); ++i) {
-      auto& mem = ltm_.match_memory[memory_index_[i]];
-      unsigned int count;
-      memcpy(&count, p, 4);
-      p += 4;
-      if (count < (5.0 / 9.0) * mem.table.size()) {
-        for (unsigned int k = 0; k < count; ++k) {
-          unsigned int key;
-          memcpy(&key, p, 4);
-          memcpy(mem.table[key].data(), p + 4, 5);
-          p += 9;
-        }
-      } else {
-        memcpy(mem.table.data(), p, 5 * mem.table.size());
-        p += 5 * mem.table.size();
-      }
-      memcpy(mem.predictions.data(), p, 1024);
-      memcpy(mem.counts.data(), p + 1024, 1024);
-      p += 2048;
-    }
+    sections::Source src(l.data(), l.size());
+    const unsigned char* history = nullptr;
+    uint64_t hs = 0;
+    bool ok = sections::MatchHistoryDecode(src, &history, &hs);
+    if (ok) ltm_.history.assign(history, history + hs);
+    for (size_t i = 0; ok && i < descs_.size(); ++i) ok = sections::MatchDecode(src, View(i));
+    if (!ok) Check("gmx_match_export", GMX_ERR_FORMAT);
     staged_ = true;
   }
   void Unstage() {
@@ -2174,26 +2021,10 @@ class GpuMatchBank {
     SyncIfAhead();
     import_pending_ = false;
     Unstage();
-    if (o.pool_ == pool_) {
-      Call("gmx_match_copy", [&] { return gmx_match_copy(h_, slot_, o.h_, o.slot_); });
-    } else {  // two banks: both pools' calls held off, always in address order
-      MixerPool* a = pool_.get() < o.pool_.get() ? pool_.get() : o.pool_.get();
-      MixerPool* b = pool_.get() < o.pool_.get() ? o.pool_.get() : pool_.get();
-      int rc;
-      {
-        std::lock_guard<std::mutex> la(a->mu_);
-        std::lock_guard<std::mutex> lb(b->mu_);
-        rc = gmx_match_copy(h_, slot_, o.h_, o.slot_);
-      }
-      pool_->Check("gmx::GpuMatch", "gmx_match_copy", rc);
-    }
+    CopyLocked(o, "gmx_match_copy", [&] { return gmx_match_copy(h_, slot_, o.h_, o.slot_); });
     fwd_pending_ = false;  // (gmx_match_copy drops it)
   }
 
-  ShortTermMemory& stm_;
-  LongTermMemory& ltm_;
-  std::shared_ptr<MixerPool> pool_;
-  int slot_ = 0;
   gmx_match* h_ = nullptr;
   std::vector<gmx_match_desc> descs_;
   std::vector<GpuMatch*> models_;
@@ -2202,7 +2033,7 @@ class GpuMatchBank {
   std::vector<float> pred_;
   std::vector<uint8_t> active_;
   std::vector<char> short_cache_, short_in_;
-  bool import_pending_ = false, staged_ = false;
+  bool staged_ = false;
   bool fwd_pending_ = false;  // per bit: a gmx_match_forward waits for its learn
   std::vector<float> slots_;  // ... and the slot values it reported
   bool ls_fresh_ = false;  // lock step: the stream's first Predict through the chainstep object is still to come
@@ -2428,7 +2259,7 @@ class GpuCtxVar : public Model {
 };
 
 // All context objects of one Predictor: one stream of a gmx_ctx (the Predictor's own, or a MixerPool's).
-class GpuCtxBank {
+class GpuCtxBank : public DeviceBank<GpuCtxBank> {
  public:
   // The bank of the Predictor whose ShortTermMemory holds `addr`.
   static std::shared_ptr<GpuCtxBank> ForAddress(const unsigned int* addr) {
@@ -2446,12 +2277,9 @@ class GpuCtxBank {
                       "constructed with (the device context bank needs the mixers on the device: INTEGRATION.md section 2)\n");
       abort();
     }
-    auto& reg = Registry();
-    auto it = reg.find(&mixers->ltm());
-    if (it != reg.end())
-      if (auto sp = it->second.lock()) return sp;
-    std::shared_ptr<GpuCtxBank> sp(new GpuCtxBank(mixers->stm(), mixers->ltm()));
-    reg[&mixers->ltm()] = sp;
+    bool created = false;
+    std::shared_ptr<GpuCtxBank> sp = For(mixers->stm(), mixers->ltm(), &created);
+    if (!created) return sp;
     // every object whose output field lies in this ShortTermMemory, in construction order
     const unsigned int* lo = reinterpret_cast<const unsigned int*>(&sp->stm_);
     const unsigned int* hi = reinterpret_cast<const unsigned int*>(reinterpret_cast<const char*>(&sp->stm_) + sizeof(ShortTermMemory));
@@ -2468,17 +2296,7 @@ class GpuCtxBank {
     sp->basic_ = sp->vars_.empty() ? nullptr : sp->vars_[0]->basic_;
     return sp;
   }
-  ~GpuCtxBank() {
-    {
-      std::lock_guard<std::mutex> lk(pool_->mu_);
-      st().cbank = nullptr;
-    }
-    pool_->Detach(slot_);
-    std::lock_guard<std::recursive_mutex> lk(AdapterMutex());
-    Registry().erase(&ltm_);
-  }
-  GpuCtxBank(const GpuCtxBank&) = delete;
-  GpuCtxBank& operator=(const GpuCtxBank&) = delete;
+  ~GpuCtxBank() { Retire(); }
 
   // The bank of the Predictor that owns `stm`, settled now if no object of it has been called yet; null when the
   // Predictor has no device context objects.
@@ -2492,20 +2310,10 @@ class GpuCtxBank {
   friend class GpuIndirectHash;
   friend class GpuMixerBank;
   friend class GpuBasicContexts;
-  GpuCtxBank(ShortTermMemory& stm, LongTermMemory& ltm) : stm_(stm), ltm_(ltm) {
-    pool_ = MixerPool::Attach(&ltm, &slot_);
-    std::lock_guard<std::mutex> lk(pool_->mu_);
-    st().cbank = this;
-  }
-  static std::map<const LongTermMemory*, std::weak_ptr<GpuCtxBank>>& Registry() {
-    static std::map<const LongTermMemory*, std::weak_ptr<GpuCtxBank>> r;
-    return r;
-  }
-  MixerPool::Stream& st() { return pool_->streams_[slot_]; }
-  template <class F>
-  void Call(const char* what, F f) {
-    pool_->Call("gmx::GpuCtxBank", what, f);
-  }
+  friend class DeviceBank<GpuCtxBank>;
+  static constexpr const char* kWho = "gmx::GpuCtxBank";
+  static constexpr auto kBack = &MixerPool::Stream::cbank;
+  GpuCtxBank(ShortTermMemory& stm, LongTermMemory& ltm) : DeviceBank(stm, ltm, this) {}
   [[noreturn]] static void Refuse(const std::string& why) {
     fprintf(stderr, "\ngmx::GpuCtxBank: %s\n(the context objects of this Predictor cannot be described to gmx_ctx_create; "
                     "there is no CPU fallback)\n", why.c_str());
@@ -2607,10 +2415,6 @@ class GpuCtxBank {
       fprintf(stderr, "\n");
     }
   }
-  void SyncIfAhead() {
-    MixerPool::Stream& s = st();
-    if (s.ra && s.mixers) s.mixers->SyncRunAhead();
-  }
   // Ensure, then what a ReadCheckpoint or a Copy left to do: the hash sections read from the .short stream go to the
   // device, and the board is built from the ShortTermMemory as it stands now (restored, or copied -- ShortTermMemory's
   // serialiser and Copy both skip last_two_bytes_hash, short-term-memory.cpp:3-59, :119-176: the field keeps the value
@@ -2699,11 +2503,10 @@ class GpuCtxBank {
   void Stage() {
     Settle();
     SyncIfAhead();
-    size_t n = 0;
     export_off_.assign((size_t)n_hash_ + 1, 0);
-    Call("gmx_ctx_export", [&] { return gmx_ctx_export(h_, slot_, nullptr, &n, export_off_.data()); });
-    export_buf_.assign(n ? n : 1, 0);
-    Call("gmx_ctx_export", [&] { return gmx_ctx_export(h_, slot_, export_buf_.data(), &n, export_off_.data()); });
+    std::vector<char> none;
+    Export("gmx_ctx_export", &export_buf_, &none,
+           [&](char* p, size_t* n, char*, size_t*) { return gmx_ctx_export(h_, slot_, p, n, export_off_.data()); });
   }
   void CopyFrom(GpuCtxBank& o) {
     o.Settle();
@@ -2712,28 +2515,12 @@ class GpuCtxBank {
     Ensure();
     SyncIfAhead();
     import_pending_ = false;
-    if (o.pool_ == pool_) {
-      Call("gmx_ctx_copy", [&] { return gmx_ctx_copy(h_, slot_, o.h_, o.slot_); });
-    } else {  // two banks: both pools' calls held off, always in address order
-      MixerPool* a = pool_.get() < o.pool_.get() ? pool_.get() : o.pool_.get();
-      MixerPool* b = pool_.get() < o.pool_.get() ? o.pool_.get() : pool_.get();
-      int rc;
-      {
-        std::lock_guard<std::mutex> la(a->mu_);
-        std::lock_guard<std::mutex> lb(b->mu_);
-        rc = gmx_ctx_copy(h_, slot_, o.h_, o.slot_);
-      }
-      pool_->Check("gmx::GpuCtxBank", "gmx_ctx_copy", rc);
-    }
+    CopyLocked(o, "gmx_ctx_copy", [&] { return gmx_ctx_copy(h_, slot_, o.h_, o.slot_); });
     // ShortTermMemory::Copy follows (predictor.cpp:42-48) and is not quite a copy (last_two_bytes_hash stays): the board
     // is made from this Predictor's own ShortTermMemory at the next call, as after a ReadCheckpoint
     board_pending_ = true;
   }
 
-  ShortTermMemory& stm_;
-  LongTermMemory& ltm_;
-  std::shared_ptr<MixerPool> pool_;
-  int slot_ = 0;
   gmx_ctx* h_ = nullptr;
   GpuBasicContexts* basic_ = nullptr;
   std::vector<GpuCtxVar*> vars_;  // the objects, in construction order: variables [0, vars_.size())
@@ -2743,8 +2530,8 @@ class GpuCtxBank {
   std::vector<uint32_t> values_;
   std::vector<char> import_buf_, export_buf_;
   std::vector<size_t> export_off_;
-  bool import_pending_ = false, board_pending_ = false;
-  bool learned_ = false;    // the board's new_bit is the newest coded bit
+  bool board_pending_ = false;
+  bool learned_ = false;   // the board's new_bit is the newest coded bit
   bool forwarded_ = false;  // per bit: a gmx_ctx_forward waits for its learn
 };
 
@@ -2872,15 +2659,6 @@ class GpuIndirectHash : public GpuCtxVar {
 };
 
 // ---- the parts of the mixers' bank that know the other two ---------------------------------------------------
-inline void GpuMatchBank::SyncIfAhead() {
-  MixerPool::Stream& s = st();
-  if (s.ra && s.mixers) s.mixers->SyncRunAhead();
-}
-inline void GpuLstmModel::SyncIfAhead() {
-  MixerPool::Stream& s = st();
-  if (s.ra && s.mixers) s.mixers->SyncRunAhead();
-}
-
 inline std::vector<int> GpuMixerBank::IndirectSlots() const {
   std::vector<int> v;
   const GpuIndirectBank* ib = pool_->streams_[slot_].indirect;

@@ -33,6 +33,7 @@
 #include <numeric>
 
 #include "gmx_mixer.h"
+#include "gmx_sections.h"  // how long the sparse .long sections are
 #include "../../include/gmxmix_lstm_group.h"  // gmx::LstmBank::ExportAll / ImportAll
 
 namespace gmx {
@@ -83,8 +84,7 @@ class IndirectBank {
   }
   void ReadFromDisk(std::ifstream* s) {
     if (!h_) return;
-    // per model: u32 count, then count x {u32 key, u8, u8} if sparse (count < size / 3) else the
-    // two whole tables, then 2 x 256 floats
+    // per model: u32 count, the sparse entries or the two whole tables, 2 x 256 floats (gmx_sections.h)
     std::vector<char> buf;
     auto take = [&](size_t n) {
       size_t at = buf.size();
@@ -92,12 +92,11 @@ class IndirectBank {
       s->read(buf.data() + at, n);
     };
     for (const gmx_indirect_desc& d : descs_) {
-      const uint64_t size = (uint64_t)d.table_size * 256u + 1u;
       take(4);
       uint32_t count;
       memcpy(&count, buf.data() + buf.size() - 4, 4);
-      take(count < size / 3 ? (size_t)count * 6 : (size_t)size * 2);
-      take(2 * 256 * 4);
+      take(sections::IndirectPayload(count, sections::IndirectSize(d.table_size)));
+      take(sections::kTrailer);
     }
     Note(gmx_indirect_import(h_, 0, buf.data(), buf.size()));
   }
@@ -279,9 +278,8 @@ class MatchBank {
       take(4);
       uint32_t count;
       memcpy(&count, buf.data() + buf.size() - 4, 4);
-      // (match.cpp's rule, in double: sparse records below 5/9 of the table)
-      take((double)count < (5.0 / 9.0) * (double)d.table_size ? (size_t)count * 9 : (size_t)d.table_size * 5);
-      take(2 * 256 * 4);
+      take(sections::MatchPayload(count, d.table_size));
+      take(sections::kTrailer);
     }
     Note(gmx_match_import(h_, stream, buf.data(), buf.size(), short_in_.data(), short_in_.size()));
   }
