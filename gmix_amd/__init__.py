@@ -5,10 +5,10 @@ from . import topology
 from ._lib import ABI_SYMBOLS, LIB_PATH, GmxError, build
 from .bank import Batch, ChainStep, Lockstep, MixerGroup, Topology, device_count
 from .indirect import IndirectBatch, IndirectGroup
-from .lstm import LstmBatch, LstmGroup
+from .lstm import LstmBatch, LstmGroup, LstmShape
 from .match import MatchBatch, MatchGroup
 from .ctx import CtxBatch, CtxGroup
 
 __all__ = ["topology", "ABI_SYMBOLS", "LIB_PATH", "GmxError", "build", "Batch", "MixerGroup",
-           "Lockstep", "ChainStep", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch",
+           "Lockstep", "ChainStep", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch", "LstmShape",
            "MatchGroup", "MatchBatch", "CtxGroup", "CtxBatch"]

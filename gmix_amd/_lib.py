@@ -304,10 +304,23 @@ def lib():
             f.restype = vp
         L.gmx_debug_chainstep_bit_launches.argtypes = [vp]
         L.gmx_debug_chainstep_bit_launches.restype = C.c_int64
+    if hasattr(L, "gmx_lstm_create_shaped"):
+        # (include/gmxmix_lstm_shape.h; an older build loaded through GMX_LIB for a comparison lacks them, and a call fails)
+        L.gmx_lstm_shape_supported.argtypes = [C.POINTER(LstmShapeC)]
+        L.gmx_lstm_create_shaped.argtypes = [C.POINTER(vp), C.POINTER(LstmShapeC), i32, i32]
+        L.gmx_lstm_get_shape.argtypes = [vp, C.POINTER(LstmShapeC)]
+        L.gmx_debug_lstm_any_launches.argtypes = [vp]
+        L.gmx_debug_lstm_any_launches.restype = C.c_int64
     L.gmx_debug_math_probe.argtypes = [i32, vp, vp, u64, i32]
     L.gmx_debug_math_range.argtypes = [i32, u64, u64, i32, C.POINTER(C.c_ulonglong)]
     _LIB = L
     return L
+
+
+class LstmShapeC(C.Structure):
+    """gmx_lstm_shape of include/gmxmix_lstm_shape.h."""
+    _fields_ = [("num_cells", C.c_int32), ("horizon", C.c_int32), ("learning_rate", C.c_float),
+                ("gradient_clip", C.c_float)]
 
 
 def check(status, where):
@@ -375,4 +388,9 @@ ABI_SYMBOLS_DECODER = [
     "gmx_chainstep_decoder_state", "gmx_chainstep_take", "gmx_chainstep_byte", "gmx_chainstep_byte_launch",
     "gmx_chainstep_byte_wait", "gmx_chainstep_timed_byte", "gmx_chainstep_decoded", "gmx_chainstep_byte_p",
     "gmx_debug_chainstep_bit_launches",
+]
+
+# What include/gmxmix_lstm_shape.h declares: an LSTM bank of any width and horizon.
+ABI_SYMBOLS_LSTM_SHAPE = [
+    "gmx_lstm_shape_supported", "gmx_lstm_create_shaped", "gmx_lstm_get_shape", "gmx_debug_lstm_any_launches",
 ]

@@ -13,6 +13,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <map>
 #include <new>
@@ -22,6 +23,7 @@
 #include "../../include/gmxmix.h"
 #include "../../include/gmxmix_lstm_group.h"
 #include "../../include/gmxmix_decoder.h"
+#include "../../include/gmxmix_lstm_shape.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
@@ -30,6 +32,7 @@
 #include "gmx_ckpt_stage.h"
 #include "gmx_ind_ckpt.h"
 #include "gmx_lstm_ckpt.h"
+#include "gmx_lstm_any.h"
 #include "gmx_match.h"
 #include "gmx_match_ckpt.h"
 #include "gmx_ctx.h"
@@ -1546,6 +1549,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 
 #include "gmx_indirect.inc"
 #include "gmx_ind_ckpt.inc"
+#include "gmx_lstm_any.inc"
 #include "gmx_lstm.inc"
 #include "gmx_lstm_ckpt.inc"
 #include "gmx_match.inc"

@@ -489,6 +489,7 @@ extern "C" int gmx_chainstep_create(gmx_chainstep** out, gmx_group* g, gmx_indir
   if (ib && (ib->S != g->S || ib->device != g->device || t.mask_words > 8)) return GMX_ERR_INVALID;
   if (l && (l->S != g->S || l->device != g->device || lstm_slot < 0 || lstm_slot >= t.n || mixer_ctx_col >= t.m))
     return GMX_ERR_INVALID;
+  if (l && l->any) return GMX_ERR_INVALID;  // the chain's launches are the stock kernel's, on the stock layout
   if (l && ib && ind_ctx_col >= ib->dev.k) return GMX_ERR_INVALID;
   if (ib)
     for (int i = 0; i < ib->dev.k; ++i)

@@ -57,7 +57,16 @@ struct gmx_lstm {
   bool use_sessions = true;
   bool banks_in_use_by_dead_kernel = false;  // a session block that stopped answering may still hold them: never freed
   struct GmxLstmCkptState* ckpt = nullptr;  // gmx_lstm_group_export / _import: layout tables and staging (gmx_lstm_ckpt.inc), lazily
+  // The shape (gmx_lstm_create_shaped).  any == false: the stock shape on the GMX_L_* layout, run by gmx_lstm.hip.
+  // any == true: any other shape -- or the stock one created under GMX_LSTM_BUILD=any -- on the layout of
+  // gmx_lstm_any.h, run by gmx_lstm_any.hip; `dev` then holds adev.o, so that what only needs offsets reads one place
+  gmx_lstm_shape shape = kLstmStockShape;
+  bool any = false;
+  GmxLstmAnyDev adev;
+  GmxLstmAnyDev* adev_d = nullptr;
+  int64_t any_launches = 0;
 };
+static LstmDims lstm_dims(const gmx_lstm* l) { return lstm_dims_of(l->shape, l->any); }
 static void lstm_ckpt_free(gmx_lstm* l);
 
 // ---- per-byte sessions: gmx_lstm_forward / gmx_lstm_perceive without a kernel launch per call -----------
@@ -85,7 +94,18 @@ extern "C" hipError_t gmx_launch_lstm_session(const GmxLstmDev* dv, const GmxLst
 extern "C" hipError_t gmx_launch_lstm_kernel(const GmxLstmDev* dv, const GmxLstmRunArgs* args, int n_streams, int cus,
                                              hipStream_t stream);
 
-static void lstm_layout(GmxLstmDev* d) {
+// The bank layout of a shape: the stock one's offsets are what they always were (its kernels read the compile-time
+// GMX_L_* extents); any other comes from lstm_layout_any (gmx_lstm_any.inc)
+static void lstm_layout_stock(GmxLstmDev* d);
+static void lstm_layout(gmx_lstm* l) {
+  if (l->any) {
+    lstm_layout_any(&l->adev, l->shape);
+    l->dev = l->adev.o;
+  } else {
+    lstm_layout_stock(&l->dev);
+  }
+}
+static void lstm_layout_stock(GmxLstmDev* d) {
   uint64_t off = 0;
   auto take = [&off](uint64_t n) {
     uint64_t o = off;
@@ -145,6 +165,7 @@ extern "C" void gmx_lstm_destroy(gmx_lstm* l) {
   if (!l->banks_in_use_by_dead_kernel) {  // (as gmx_group_destroy: leaked rather than freed under a running kernel)
     if (l->banks) (void)hipFree(l->banks);
     if (l->dev_d) (void)hipFree(l->dev_d);
+    if (l->adev_d) (void)hipFree(l->adev_d);
   }
   for (int k = 0; k < gmx_lstm::kAdamSlots; ++k) {
     if (l->adam_host[k]) (void)hipHostFree(l->adam_host[k]);
@@ -173,11 +194,12 @@ extern "C" int gmx_lstm_reset(gmx_lstm* l) {
   LSTM_CLOSE_SESSIONS(l);
   std::vector<float> img(l->dev.bank_floats, 0.0f);
   const GmxLstmDev& d = l->dev;
+  const LstmDims k = lstm_dims(l);
   for (int g = 0; g < 3; ++g)
-    for (int i = 0; i < GMX_L_NC; ++i) img[d.gate[g].gamma + i] = 1.0f;
-  img[d.hidden + GMX_L_HID - 1] = 1.0f;
-  for (int e = 0; e < GMX_L_H; ++e) {
-    img[d.layer_input + (uint64_t)e * GMX_L_LINP + GMX_L_LIN - 1] = 1.0f;
+    for (int i = 0; i < k.NC; ++i) img[d.gate[g].gamma + i] = 1.0f;
+  img[d.hidden + k.HID - 1] = 1.0f;
+  for (int e = 0; e < k.H; ++e) {
+    img[d.layer_input + (uint64_t)e * k.LINP + k.LIN - 1] = 1.0f;
     for (int i = 0; i < GMX_L_NO; ++i) img[d.output + (uint64_t)e * GMX_L_NO + i] = (float)(1.0 / GMX_L_NO);
   }
   for (int i = 0; i < GMX_L_NO; ++i) img[d.probs + i] = (float)(1.0 / 256);
@@ -191,10 +213,10 @@ extern "C" int gmx_lstm_reset(gmx_lstm* l) {
   return GMX_OK;
 }
 
-extern "C" int gmx_lstm_create(gmx_lstm** out, int n_streams, int device) {
+static int lstm_create(gmx_lstm** out, const gmx_lstm_shape& shape, int n_streams, int device) {
   if (!out) return GMX_ERR_INVALID;
   *out = nullptr;
-  if (n_streams < 1) return GMX_ERR_INVALID;
+  if (n_streams < 1 || !gmx_lstm_shape_supported(&shape)) return GMX_ERR_INVALID;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     (void)hipGetLastError();
@@ -207,7 +229,10 @@ extern "C" int gmx_lstm_create(gmx_lstm** out, int n_streams, int device) {
   l->device = device;
   batch_bank_init(l->bb, l, device, &l->stream, &l->up_stream, &l->down_stream);
   l->S = n_streams;
-  lstm_layout(&l->dev);
+  l->shape = shape;
+  l->any = !lstm_shape_is_stock(shape) || lstm_env_forces_any();
+  l->use_sessions = !l->any;  // (the per-byte session is a build of the stock kernel)
+  lstm_layout(l);
   l->bytes_seen.assign(n_streams, 0);
   l->update_steps.assign(n_streams, 0);
   l->fwd_done.assign(n_streams, 0);
@@ -231,6 +256,10 @@ extern "C" int gmx_lstm_create(gmx_lstm** out, int n_streams, int device) {
   LCHK(hipEventCreate(&l->ev1));
   LCHK(hipMalloc((void**)&l->dev_d, sizeof(GmxLstmDev)));
   LCHK(hipMemcpy(l->dev_d, &l->dev, sizeof(GmxLstmDev), hipMemcpyHostToDevice));
+  if (l->any) {
+    LCHK(hipMalloc((void**)&l->adev_d, sizeof(GmxLstmAnyDev)));
+    LCHK(hipMemcpy(l->adev_d, &l->adev, sizeof(GmxLstmAnyDev), hipMemcpyHostToDevice));
+  }
   LCHK(hipMalloc((void**)&l->banks, (size_t)n_streams * l->dev.bank_floats * sizeof(float)));
 #undef LCHK
   int rc = gmx_lstm_reset(l);
@@ -241,6 +270,21 @@ extern "C" int gmx_lstm_create(gmx_lstm** out, int n_streams, int device) {
   *out = l;
   return GMX_OK;
 }
+
+extern "C" int gmx_lstm_create(gmx_lstm** out, int n_streams, int device) {
+  return lstm_create(out, kLstmStockShape, n_streams, device);
+}
+extern "C" int gmx_lstm_create_shaped(gmx_lstm** out, const gmx_lstm_shape* shape, int n_streams, int device) {
+  if (out) *out = nullptr;
+  if (!shape) return GMX_ERR_INVALID;
+  return lstm_create(out, *shape, n_streams, device);
+}
+extern "C" int gmx_lstm_get_shape(const gmx_lstm* l, gmx_lstm_shape* out) {
+  if (!l || !out) return GMX_ERR_INVALID;
+  *out = l->shape;
+  return GMX_OK;
+}
+extern "C" int64_t gmx_debug_lstm_any_launches(const gmx_lstm* l) { return l ? l->any_launches : -1; }
 
 extern "C" int gmx_lstm_n_streams(const gmx_lstm* l) { return l ? l->S : GMX_ERR_INVALID; }
 extern "C" uint64_t gmx_lstm_bank_bytes(const gmx_lstm* l) { return l ? l->dev.bank_floats * 4 : 0; }
@@ -259,11 +303,12 @@ extern "C" int gmx_lstm_set_weights(gmx_lstm* l, int stream, const float* w) {
   HIPCHK(hipSetDevice(l->device));
   LSTM_CLOSE_SESSIONS(l);
   HIPCHK(hipStreamSynchronize(l->stream));
-  std::vector<float> t((size_t)GMX_L_MAT_FLOATS, 0.0f);
+  const LstmDims k = lstm_dims(l);
+  std::vector<float> t((size_t)k.mat_floats, 0.0f);
   for (int g = 0; g < 3; ++g) {
     std::fill(t.begin(), t.end(), 0.0f);
-    for (int i = 0; i < GMX_L_NC; ++i)
-      for (int j = 0; j < GMX_L_W; ++j) t[gmx_l_mat(j, i)] = w[((size_t)g * GMX_L_NC + i) * GMX_L_W + j];
+    for (int i = 0; i < k.NC; ++i)
+      for (int j = 0; j < k.W; ++j) t[k.mat(j, i)] = w[((size_t)g * k.NC + i) * k.W + j];
     HIPCHK(hipMemcpy(l->banks + (size_t)stream * l->dev.bank_floats + l->dev.gate[g].weights, t.data(), t.size() * 4,
                      hipMemcpyHostToDevice));
   }
@@ -277,20 +322,21 @@ extern "C" int gmx_lstm_get_weights(gmx_lstm* l, int stream, float* w, float* ou
   HIPCHK(hipSetDevice(l->device));
   LSTM_CLOSE_SESSIONS(l);
   HIPCHK(hipStreamSynchronize(l->stream));
-  std::vector<float> t((size_t)GMX_L_MAT_FLOATS);
+  const LstmDims k = lstm_dims(l);
+  std::vector<float> t((size_t)k.mat_floats);
   const float* bank = l->banks + (size_t)stream * l->dev.bank_floats;
   for (int g = 0; g < 3; ++g) {
     HIPCHK(hipMemcpy(t.data(), bank + l->dev.gate[g].weights, t.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < GMX_L_NC; ++i)
-      for (int j = 0; j < GMX_L_W; ++j) w[((size_t)g * GMX_L_NC + i) * GMX_L_W + j] = t[gmx_l_mat(j, i)];
+    for (int i = 0; i < k.NC; ++i)
+      for (int j = 0; j < k.W; ++j) w[((size_t)g * k.NC + i) * k.W + j] = t[k.mat(j, i)];
   }
   if (output_layer) {
-    std::vector<float> o((size_t)GMX_L_H * GMX_L_HID * GMX_L_NO);
+    std::vector<float> o((size_t)k.H * k.HID * GMX_L_NO);
     HIPCHK(hipMemcpy(o.data(), bank + l->dev.out_layer, o.size() * 4, hipMemcpyDeviceToHost));
-    for (int e = 0; e < GMX_L_H; ++e)
+    for (int e = 0; e < k.H; ++e)
       for (int i = 0; i < GMX_L_NO; ++i)
-        for (int j = 0; j < GMX_L_HID; ++j)
-          output_layer[((size_t)e * GMX_L_NO + i) * GMX_L_HID + j] = o[((size_t)e * GMX_L_HID + j) * GMX_L_NO + i];
+        for (int j = 0; j < k.HID; ++j)
+          output_layer[((size_t)e * GMX_L_NO + i) * k.HID + j] = o[((size_t)e * k.HID + j) * GMX_L_NO + i];
   }
   return GMX_OK;
 }
@@ -339,8 +385,9 @@ extern "C" int gmx_lstm_batch_wait(gmx_lstm_batch* b) { return batch_core_wait(b
 // that say when passes fall (bytes_seen, update_steps).  n_list (nullable, [ns]): a byte count per stream.
 static void lstm_stage_rows(gmx_lstm* l, int s0, int ns, uint64_t n_bytes, int learn, unsigned phases,
                             const uint64_t* n_list, float* adam_host, uint32_t max_bptt) {
-  const float beta1 = 0.025, beta2 = 0.9999, learning_rate = 0.03f;
+  const float beta1 = 0.025, beta2 = 0.9999, learning_rate = l->shape.learning_rate;
   const unsigned long long limit = 3000;
+  const uint64_t horizon = (uint64_t)l->shape.horizon;
   const bool perceives = learn && (phases & 4u);
   for (int i = 0; i < ns; ++i) {
     const int s = s0 + i;
@@ -350,7 +397,7 @@ static void lstm_stage_rows(gmx_lstm* l, int s0, int ns, uint64_t n_bytes, int l
     for (uint64_t n = 0; n < nb && perceives; ++n) {
       // Lstm::Perceive runs its backward pass when epoch_ has wrapped to 0 (lstm.cpp:57), and
       // epoch_ counts Lstm::Predict calls (learned from or not)
-      if ((l->bytes_seen[s] + ((phases & 1u) ? n + 1 : 0)) % GMX_L_H != 0) continue;
+      if ((l->bytes_seen[s] + ((phases & 1u) ? n + 1 : 0)) % horizon != 0) continue;
       if (steps < limit) ++steps;
       const float t = (float)steps;
       float* row = adam_host + ((size_t)i * max_bptt + k) * 4;
@@ -380,7 +427,7 @@ static int lstm_launch(gmx_lstm* l, gmx_lstm_batch* b, int s0, int ns, uint64_t 
   // n_list (host, [ns]): bytes of each stream of the range, at most n_bytes (one launch for streams of different lengths)
   // Adam's scalars (lstm-layer.cpp:15-21, :27-32) depend on the step count only: computed here
   // with the libm the reference calls (powf, sqrtf), one row per backward pass of each stream
-  const uint32_t max_bptt = (uint32_t)(n_bytes / GMX_L_H + 2);
+  const uint32_t max_bptt = (uint32_t)(n_bytes / (uint64_t)l->shape.horizon + 2);
   const size_t need = (size_t)ns * max_bptt * 4;
   const int slot = (int)(l->adam_seq++ % gmx_lstm::kAdamSlots);
   if (l->adam_busy[slot]) {
@@ -434,7 +481,12 @@ static int lstm_launch(gmx_lstm* l, gmx_lstm_batch* b, int s0, int ns, uint64_t 
     if (rcx) return rcx;
   }
   if (kernel_ms) HIPCHK(hipEventRecord(l->ev0, l->stream));
-  HIPCHK(gmx_launch_lstm_kernel(l->dev_d, &a, ns, l->cus, l->stream));
+  if (l->any) {
+    HIPCHK(gmx_launch_lstm_any_kernel(l->adev_d, &a, ns, l->stream));
+    ++l->any_launches;
+  } else {
+    HIPCHK(gmx_launch_lstm_kernel(l->dev_d, &a, ns, l->cus, l->stream));
+  }
   HIPCHK(hipEventRecord(l->adam_done[slot], l->stream));
   l->adam_busy[slot] = true;
   if (n_list) {
@@ -578,8 +630,8 @@ static void lstm_sessions_free(gmx_lstm* l) {
 // (lstm_launch has the same for a batch): Lstm::Perceive runs it when epoch_ has wrapped to 0 (lstm.cpp:57).
 static void lstm_perceive_scalars(gmx_lstm* l, int s, float row[4]) {
   row[0] = row[1] = row[2] = row[3] = 0.0f;
-  if (l->bytes_seen[s] % GMX_L_H != 0) return;
-  const float beta1 = 0.025, beta2 = 0.9999, learning_rate = 0.03f;
+  if (l->bytes_seen[s] % (uint64_t)l->shape.horizon != 0) return;
+  const float beta1 = 0.025, beta2 = 0.9999, learning_rate = l->shape.learning_rate;
   const unsigned long long limit = 3000;
   uint32_t steps = l->update_steps[s];
   if (steps < limit) ++steps;
@@ -691,7 +743,7 @@ extern "C" int gmx_debug_lstm_use_sessions(gmx_lstm* l, int on) {
   if (!l) return GMX_ERR_INVALID;
   HIPCHK(hipSetDevice(l->device));
   LSTM_CLOSE_SESSIONS(l);
-  l->use_sessions = on != 0;
+  l->use_sessions = on != 0 && !l->any;  // (a bank on the general layout never starts a session)
   return GMX_OK;
 }
 
@@ -785,11 +837,12 @@ extern "C" int gmx_lstm_feed(gmx_lstm* l, gmx_lstm_batch* b, uint64_t n_bytes, g
 // the eighth LstmModel::Predict of the last coded byte left (lstm-model.cpp:34-41).
 namespace {
 
-constexpr size_t kLstmLongBytes = ((size_t)GMX_L_H * GMX_L_NO * GMX_L_HID + 3u * GMX_L_NC * GMX_L_W) * 4u;
+size_t lstm_long_bytes(const LstmDims& k) { return ((size_t)k.H * GMX_L_NO * k.HID + 3u * (size_t)k.NC * k.W) * 4u; }
 
 // One pass over the `.short` layout; `dir` false: bank image -> file bytes, true: file -> image.
 struct LstmShortIo {
   const GmxLstmDev& d;
+  const LstmDims& k;
   std::vector<float>& img;  // host copy of one bank
   uint8_t* buf;             // file bytes (null: count only)
   bool rd;
@@ -805,23 +858,23 @@ struct LstmShortIo {
   void rows(uint64_t at, int rows_, int n, int pitch) {
     for (int r = 0; r < rows_; ++r) raw(&img[at + (uint64_t)r * pitch], (size_t)n * 4);
   }
-  // a reference [cell][W] matrix, stored in the bank input-major (gmx_l_mat)
+  // a reference [cell][W] matrix, stored in the bank input-major (LstmDims::mat)
   void cell_major(uint64_t at) {
-    for (int i = 0; i < GMX_L_NC; ++i)
-      for (int j = 0; j < GMX_L_W; ++j) raw(&img[at + gmx_l_mat(j, i)], 4);
+    for (int i = 0; i < k.NC; ++i)
+      for (int j = 0; j < k.W; ++j) raw(&img[at + k.mat(j, i)], 4);
   }
 };
 
-size_t lstm_short_io(const GmxLstmDev& d, std::vector<float>& img, uint8_t* buf, bool rd, int32_t tmb[3],
-                     uint32_t* epoch, uint32_t* l_epoch, uint64_t* update_steps) {
-  LstmShortIo io{d, img, buf, rd};
-  const int H = GMX_L_H, NC = GMX_L_NC, CP = GMX_L_CP;
+size_t lstm_short_io(const GmxLstmDev& d, const LstmDims& k, std::vector<float>& img, uint8_t* buf, bool rd,
+                     int32_t tmb[3], uint32_t* epoch, uint32_t* l_epoch, uint64_t* update_steps) {
+  LstmShortIo io{d, k, img, buf, rd};
+  const int H = k.H, NC = k.NC, CP = k.CP;
   io.raw(tmb, 12);
   io.rows(d.probs, 1, GMX_L_NO, 0);
   io.rows(d.input_history, 1, H, 0);
-  io.rows(d.hidden, 1, GMX_L_HID, 0);
+  io.rows(d.hidden, 1, k.HID, 0);
   io.rows(d.hidden_error, 1, NC, 0);
-  io.rows(d.layer_input, H, GMX_L_LIN, GMX_L_LINP);
+  io.rows(d.layer_input, H, k.LIN, k.LINP);
   io.rows(d.output, H, GMX_L_NO, GMX_L_NO);
   io.raw(epoch, 4);
   io.rows(d.state, 1, NC, 0);
@@ -834,8 +887,9 @@ size_t lstm_short_io(const GmxLstmDev& d, std::vector<float>& img, uint8_t* buf,
   io.raw(update_steps, 8);
   for (int g = 0; g < 3; ++g) {
     const GmxLstmGateOff& o = d.gate[g];
-    // error_: what the last step (epoch 0) of the last backward pass left (lstm-layer.cpp:311-316)
-    io.rows(d.errs + (uint64_t)g * H * CP, 1, NC, 0);
+    // error_: what the last step (epoch 0) of the last backward pass left (lstm-layer.cpp:311-316); the general
+    // layout keeps the vector itself
+    io.rows(k.any ? o.error : d.errs + (uint64_t)g * H * CP, 1, NC, 0);
     io.rows(o.ivar, 1, H, 0);
     const uint64_t vecs[] = {o.gamma, o.gamma_u, o.gamma_m, o.gamma_v, o.beta, o.beta_u, o.beta_m, o.beta_v};
     for (uint64_t v : vecs) io.rows(v, 1, NC, 0);
@@ -843,18 +897,18 @@ size_t lstm_short_io(const GmxLstmDev& d, std::vector<float>& img, uint8_t* buf,
     io.cell_major(o.update);
     io.cell_major(o.m);
     io.cell_major(o.v);
-    io.rows(o.transpose, GMX_L_HID, NC, CP);
+    io.rows(o.transpose, k.HID, NC, CP);
     io.rows(o.norm, H, NC, CP);
   }
   return io.off;
 }
 
-size_t lstm_long_io(const GmxLstmDev& d, std::vector<float>& img, uint8_t* buf, bool rd) {
-  LstmShortIo io{d, img, buf, rd};
+size_t lstm_long_io(const GmxLstmDev& d, const LstmDims& k, std::vector<float>& img, uint8_t* buf, bool rd) {
+  LstmShortIo io{d, k, img, buf, rd};
   // lstm_output_layer[epoch][symbol][hidden], stored in the bank as [epoch][hidden][symbol]
-  for (int e = 0; e < GMX_L_H; ++e)
+  for (int e = 0; e < k.H; ++e)
     for (int i = 0; i < GMX_L_NO; ++i)
-      for (int j = 0; j < GMX_L_HID; ++j) io.raw(&img[d.out_layer + ((uint64_t)e * GMX_L_HID + j) * GMX_L_NO + i], 4);
+      for (int j = 0; j < k.HID; ++j) io.raw(&img[d.out_layer + ((uint64_t)e * k.HID + j) * GMX_L_NO + i], 4);
   for (int g = 0; g < 3; ++g) io.cell_major(d.gate[g].weights);
   return io.off;
 }
@@ -868,14 +922,16 @@ extern "C" int gmx_lstm_export(gmx_lstm* l, int stream, void* long_buf, size_t* 
   int32_t tmb[3] = {255, 127, 0};
   uint32_t epoch = 0, l_epoch = 0;
   uint64_t steps = 0;
-  const size_t need_short = lstm_short_io(l->dev, img, nullptr, false, tmb, &epoch, &l_epoch, &steps);
+  const LstmDims k = lstm_dims(l);
+  const size_t need_long = lstm_long_bytes(k);
+  const size_t need_short = lstm_short_io(l->dev, k, img, nullptr, false, tmb, &epoch, &l_epoch, &steps);
   if (!long_buf && !short_buf) {
-    *long_bytes = kLstmLongBytes;
+    *long_bytes = need_long;
     *short_bytes = need_short;
     return GMX_OK;
   }
-  if ((long_buf && *long_bytes < kLstmLongBytes) || (short_buf && *short_bytes < need_short)) {
-    *long_bytes = kLstmLongBytes;
+  if ((long_buf && *long_bytes < need_long) || (short_buf && *short_bytes < need_short)) {
+    *long_bytes = need_long;
     *short_bytes = need_short;
     return GMX_ERR_INVALID;
   }
@@ -899,8 +955,8 @@ extern "C" int gmx_lstm_export(gmx_lstm* l, int stream, void* long_buf, size_t* 
     tmb[1] = tmb[2];
     tmb[0] = tmb[2] + 1;
   }
-  if (long_buf) *long_bytes = lstm_long_io(l->dev, img, (uint8_t*)long_buf, false);
-  if (short_buf) *short_bytes = lstm_short_io(l->dev, img, (uint8_t*)short_buf, false, tmb, &epoch, &l_epoch, &steps);
+  if (long_buf) *long_bytes = lstm_long_io(l->dev, k, img, (uint8_t*)long_buf, false);
+  if (short_buf) *short_bytes = lstm_short_io(l->dev, k, img, (uint8_t*)short_buf, false, tmb, &epoch, &l_epoch, &steps);
   return GMX_OK;
 }
 
@@ -911,12 +967,13 @@ extern "C" int gmx_lstm_import(gmx_lstm* l, int stream, const void* long_buf, si
   int32_t tmb[3] = {255, 127, 0};
   uint32_t epoch = 0, l_epoch = 0;
   uint64_t steps = 0;
-  if (long_bytes != kLstmLongBytes ||
-      short_bytes != lstm_short_io(l->dev, img, nullptr, true, tmb, &epoch, &l_epoch, &steps))
+  const LstmDims k = lstm_dims(l);
+  if (long_bytes != lstm_long_bytes(k) ||
+      short_bytes != lstm_short_io(l->dev, k, img, nullptr, true, tmb, &epoch, &l_epoch, &steps))
     return GMX_ERR_FORMAT;
   const GmxLstmDev& d = l->dev;
-  lstm_long_io(d, img, (uint8_t*)const_cast<void*>(long_buf), true);
-  lstm_short_io(d, img, (uint8_t*)const_cast<void*>(short_buf), true, tmb, &epoch, &l_epoch, &steps);
+  lstm_long_io(d, k, img, (uint8_t*)const_cast<void*>(long_buf), true);
+  lstm_short_io(d, k, img, (uint8_t*)const_cast<void*>(short_buf), true, tmb, &epoch, &l_epoch, &steps);
   const float* probs = &img[d.probs];
   // a model nobody has run: the constructor's range and byte distribution (lstm-model.cpp:7-10)
   bool fresh = tmb[0] == 255 && tmb[1] == 127 && tmb[2] == 0;
@@ -925,13 +982,13 @@ extern "C" int gmx_lstm_import(gmx_lstm* l, int stream, const void* long_buf, si
   // checkpoint taken inside a byte (LstmModel::WriteToDisk works at any bit): the forward of that byte is done,
   // its Perceive still to come
   const bool boundary = !fresh && tmb[2] >= 0 && tmb[2] <= 254 && !(tmb[2] & 1) && tmb[1] == tmb[2] && tmb[0] == tmb[2] + 1;
-  if (epoch >= (uint32_t)GMX_L_H || l_epoch >= (uint32_t)GMX_L_H || steps > 3000 ||
+  if (epoch >= (uint32_t)k.H || l_epoch >= (uint32_t)k.H || steps > 3000 ||
       !(0 <= tmb[2] && tmb[2] <= tmb[1] && tmb[1] <= tmb[0] && tmb[0] <= 255))
     return GMX_ERR_FORMAT;
   // what the file leaves implicit: the constant inputs, the input-major copy of the layer inputs,
   // and the blackboard values LstmModel::Predict derives from probs_ (lstm-model.cpp:25-47)
-  img[d.hidden + GMX_L_HID - 1] = 1.0f;  // hidden_[50] (lstm.cpp:31) -- also in the file; kept as read
-  for (int e = 0; e < GMX_L_H; ++e)
+  img[d.hidden + k.HID - 1] = 1.0f;  // hidden_[num_cells] (lstm.cpp:31) -- also in the file; kept as read
+  for (int e = 0; e < GMX_L_H && !k.any; ++e)  // (the general layout has no input-major copy)
     for (int j = 0; j < GMX_L_LIN; ++j)
       img[d.lin_t + (uint64_t)j * GMX_L_HP + e] = img[d.layer_input + (uint64_t)e * GMX_L_LINP + j];
   uint32_t* scal = (uint32_t*)&img[d.scal];
@@ -944,7 +1001,7 @@ extern "C" int gmx_lstm_import(gmx_lstm* l, int stream, const void* long_buf, si
   if (!fresh) {
     // the byte itself is ShortTermMemory's to remember; Lstm::Perceive left it in input_history_ (one entry further
     // back when this byte's forward has already advanced epoch_)
-    const uint32_t newest = hist[(epoch + GMX_L_H - (boundary ? 1 : 2)) % GMX_L_H];
+    const uint32_t newest = hist[(epoch + (uint32_t)k.H - (boundary ? 1 : 2)) % (uint32_t)k.H];
     if (boundary)
       last_byte = (newest < 256 && (int32_t)(newest & 0xfeu) == tmb[2]) ? newest : (uint32_t)tmb[2];
     else
@@ -989,6 +1046,7 @@ extern "C" int gmx_lstm_import(gmx_lstm* l, int stream, const void* long_buf, si
 extern "C" int gmx_lstm_copy(gmx_lstm* dst, int dst_stream, gmx_lstm* src, int src_stream) {
   if (!dst || !src || dst_stream < 0 || dst_stream >= dst->S || src_stream < 0 || src_stream >= src->S)
     return GMX_ERR_INVALID;
+  if (dst->any != src->any || memcmp(&dst->shape, &src->shape, sizeof dst->shape) != 0) return GMX_ERR_INVALID;
   if (dst == src && dst_stream == src_stream) return GMX_OK;
   HIPCHK(hipSetDevice(src->device));
   LSTM_CLOSE_SESSIONS(src);
@@ -1011,7 +1069,8 @@ extern "C" int gmx_lstm_copy(gmx_lstm* dst, int dst_stream, gmx_lstm* src, int s
 // shape the reference builds.
 extern "C" int gmx_lstm_memory_usage(gmx_lstm* l, uint64_t* bytes) {
   if (!l || !bytes) return GMX_ERR_INVALID;
-  const uint64_t H = GMX_L_H, NC = GMX_L_NC, W = GMX_L_W, NO = GMX_L_NO, HID = GMX_L_HID, LIN = GMX_L_LIN;
+  const LstmDims k = lstm_dims(l);
+  const uint64_t H = k.H, NC = k.NC, W = k.W, NO = GMX_L_NO, HID = k.HID, LIN = k.LIN;
   const uint64_t neuron = 4 + 40 * NC + 4 * H * NC + 3 * (4 * NC * W) + 4 * (W - NO - GMX_L_NI) * NC + 4 * H * NC;
   const uint64_t layer = 44 + 3 * (4 * NC) + 3 * (4 * H * NC) + 3 * neuron;
   const uint64_t lstm = 24 + 4 * H + 4 * HID + 4 * NC + 4 * H * LIN + 4 * H * NO + layer;

@@ -73,6 +73,7 @@ extern "C" int gmx_lstm_group_export(gmx_lstm* l, int first, int count, void* lo
   if (long_stride) *long_stride = LB;
   if (short_stride) *short_stride = SB;
   if (!l || first < 0 || count < 0 || first > l->S || count > l->S - first) return GMX_ERR_INVALID;
+  if (l->any) return GMX_ERR_INVALID;  // the pack / scatter kernels know the stock layout only
   if (count == 0) return GMX_OK;
   if (!long_buf && !short_buf) return GMX_OK;  // sizing only
   if ((long_buf && long_cap < (size_t)count * LB) || (short_buf && short_cap < (size_t)count * SB))
@@ -213,6 +214,7 @@ extern "C" int gmx_lstm_group_import(gmx_lstm* l, int first, int count, const vo
                                      const void* short_buf, size_t short_bytes) {
   const size_t LB = GMX_LSTM_CKPT_LONG_BYTES, SB = GMX_LSTM_CKPT_SHORT_BYTES;
   if (!l || first < 0 || count < 0 || first > l->S || count > l->S - first) return GMX_ERR_INVALID;
+  if (l->any) return GMX_ERR_INVALID;  // the pack / scatter kernels know the stock layout only
   if (count == 0) return GMX_OK;
   if (!long_buf || !short_buf) return GMX_ERR_INVALID;
   if (long_bytes != (size_t)count * LB || short_bytes != (size_t)count * SB) return GMX_ERR_FORMAT;

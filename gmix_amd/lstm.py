@@ -7,7 +7,20 @@ import numpy as np
 from . import _lib
 from ._lib import GmxError, check
 
+from collections import namedtuple
+
 NC, W, H, NO, HID = 50, 563, 100, 256, 51
+
+# gmx_lstm_shape (include/gmxmix_lstm_shape.h): the free parameters of the reference's Lstm(256, 256, num_cells, 1,
+# horizon, learning_rate, gradient_clip, ...)
+LstmShape = namedtuple("LstmShape", "num_cells horizon learning_rate gradient_clip")
+STOCK_SHAPE = LstmShape(NC, H, 0.03, 10.0)
+
+
+def shape_supported(shape):
+    """gmx_lstm_shape_supported: host code, no device."""
+    c = _lib.LstmShapeC(int(shape[0]), int(shape[1]), float(shape[2]), float(shape[3]))
+    return bool(_lib.lib().gmx_lstm_shape_supported(C.byref(c)))
 
 
 def _vp(a):
@@ -15,12 +28,29 @@ def _vp(a):
 
 
 class LstmGroup:
-    def __init__(self, n_streams=1, device=0):
+    def __init__(self, n_streams=1, shape=None, device=0):
+        """shape: an LstmShape (or a 4-tuple); None: the stock one through gmx_lstm_create."""
         self.L = _lib.lib()
         self.S = int(n_streams)
         h = C.c_void_p()
-        check(self.L.gmx_lstm_create(C.byref(h), self.S, device), "gmx_lstm_create")
+        if shape is None:
+            check(self.L.gmx_lstm_create(C.byref(h), self.S, device), "gmx_lstm_create")
+        else:
+            c = _lib.LstmShapeC(int(shape[0]), int(shape[1]), float(shape[2]), float(shape[3]))
+            check(self.L.gmx_lstm_create_shaped(C.byref(h), C.byref(c), self.S, device), "gmx_lstm_create_shaped")
         self.h = h
+        c = _lib.LstmShapeC()
+        check(self.L.gmx_lstm_get_shape(self.h, C.byref(c)), "gmx_lstm_get_shape")
+        self._shape = LstmShape(c.num_cells, c.horizon, c.learning_rate, c.gradient_clip)
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def any_launches(self):
+        """Launches of the general kernel so far (gmx_debug_lstm_any_launches)."""
+        return int(self.L.gmx_debug_lstm_any_launches(self.h))
 
     def set_cu_mask(self, words=None):
         """Compute units this bank's kernels may use: 32-bit words, bit i = CU i (None: all)."""
@@ -51,12 +81,14 @@ class LstmGroup:
 
     def set_weights(self, w, stream=0):
         w = np.ascontiguousarray(w, np.float32)
-        assert w.shape == (3, NC, W)
+        nc = self._shape.num_cells
+        assert w.shape == (3, nc, 513 + nc)
         check(self.L.gmx_lstm_set_weights(self.h, stream, _vp(w)), "gmx_lstm_set_weights")
 
     def get_weights(self, stream=0, output_layer=True):
-        w = np.zeros((3, NC, W), np.float32)
-        o = np.zeros((H, NO, HID), np.float32) if output_layer else None
+        nc, hz = self._shape.num_cells, self._shape.horizon
+        w = np.zeros((3, nc, 513 + nc), np.float32)
+        o = np.zeros((hz, NO, nc + 1), np.float32) if output_layer else None
         check(self.L.gmx_lstm_get_weights(self.h, stream, _vp(w), _vp(o)), "gmx_lstm_get_weights")
         return w, o
 
