@@ -311,6 +311,29 @@ def lib():
         L.gmx_lstm_get_shape.argtypes = [vp, C.POINTER(LstmShapeC)]
         L.gmx_debug_lstm_any_launches.argtypes = [vp]
         L.gmx_debug_lstm_any_launches.restype = C.c_int64
+    if hasattr(L, "gmx_encoder_create"):
+        # (include/gmxmix_encoder.h; an older build loaded through GMX_LIB for a comparison lacks them, and a call fails)
+        pu64 = C.POINTER(C.c_uint64)
+        L.gmx_encoder_create.argtypes = [C.POINTER(vp), i32, u64, i32]
+        L.gmx_encoder_destroy.argtypes = [vp]
+        L.gmx_encoder_destroy.restype = None
+        L.gmx_encoder_reset.argtypes = [vp, i32, C.POINTER(u32)]
+        L.gmx_encoder_state.argtypes = [vp, i32, C.POINTER(u32)]
+        L.gmx_encoder_encode_batch.argtypes = [vp, vp, pu64, C.POINTER(C.c_float)]
+        L.gmx_encoder_encode.argtypes = [vp, vp, vp, u64, pu64]
+        L.gmx_encoder_flush.argtypes = [vp, vp]
+        for name in ("take", "take_launch", "take_wait"):
+            getattr(L, "gmx_encoder_" + name).argtypes = [vp]
+        L.gmx_encoder_bytes.argtypes = [vp, i32]
+        L.gmx_encoder_bytes.restype = vp
+        for name in ("n_bytes", "total_bytes"):
+            f = getattr(L, "gmx_encoder_" + name)
+            f.argtypes = [vp, i32]
+            f.restype = C.c_uint64
+        L.gmx_encoder_bad_bit.argtypes = [vp, i32]
+        L.gmx_encoder_bad_bit.restype = C.c_int64
+        L.gmx_debug_encoder_d2h_bytes.argtypes = [vp]
+        L.gmx_debug_encoder_d2h_bytes.restype = C.c_int64
     L.gmx_debug_math_probe.argtypes = [i32, vp, vp, u64, i32]
     L.gmx_debug_math_range.argtypes = [i32, u64, u64, i32, C.POINTER(C.c_ulonglong)]
     _LIB = L
@@ -393,4 +416,12 @@ ABI_SYMBOLS_DECODER = [
 # What include/gmxmix_lstm_shape.h declares: an LSTM bank of any width and horizon.
 ABI_SYMBOLS_LSTM_SHAPE = [
     "gmx_lstm_shape_supported", "gmx_lstm_create_shaped", "gmx_lstm_get_shape", "gmx_debug_lstm_any_launches",
+]
+
+# What include/gmxmix_encoder.h declares: the arithmetic encoder on the device.
+ABI_SYMBOLS_ENCODER = [
+    "gmx_encoder_create", "gmx_encoder_destroy", "gmx_encoder_reset", "gmx_encoder_state", "gmx_encoder_encode_batch",
+    "gmx_encoder_encode", "gmx_encoder_flush", "gmx_encoder_take", "gmx_encoder_take_launch", "gmx_encoder_take_wait",
+    "gmx_encoder_bytes", "gmx_encoder_n_bytes", "gmx_encoder_total_bytes", "gmx_encoder_bad_bit",
+    "gmx_debug_encoder_d2h_bytes",
 ]

@@ -524,3 +524,94 @@ class ChainStep:
             self.close()
         except Exception:
             pass
+
+
+class Encoder:
+    """The reference's arithmetic Encoder for S streams on the device (gmx_encoder, include/gmxmix_encoder.h): codes a
+    Batch's device bits and p, or host arrays, and returns each stream's bytes."""
+
+    def __init__(self, n_streams, max_bits, device=0):
+        self.L = _lib.lib()
+        self.S = int(n_streams)
+        self.max_bits = int(max_bits)
+        h = C.c_void_p()
+        check(self.L.gmx_encoder_create(C.byref(h), self.S, self.max_bits, device), "gmx_encoder_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gmx_encoder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _counts(self, n_bits):
+        n = np.full(self.S, n_bits, np.uint64) if np.isscalar(n_bits) else np.ascontiguousarray(n_bits, np.uint64)
+        assert n.shape == (self.S,)
+        return n
+
+    def reset(self, stream=-1, state=None):
+        """stream -1: all.  state None: a new file; otherwise the two words of a checkpoint."""
+        st = None if state is None else (C.c_uint32 * 2)(int(state[0]), int(state[1]))
+        check(self.L.gmx_encoder_reset(self.h, stream, st), "gmx_encoder_reset")
+
+    def state(self, stream):
+        out = (C.c_uint32 * 2)()
+        check(self.L.gmx_encoder_state(self.h, stream, out), "gmx_encoder_state")
+        return int(out[0]), int(out[1])
+
+    def encode_batch(self, batch, n_bits, timed=False):
+        """Bits [0, n_bits[s]) of every stream from the batch's device arrays (an int: every stream)."""
+        n = self._counts(n_bits)
+        ms = C.c_float(0)
+        check(self.L.gmx_encoder_encode_batch(self.h, batch.h, n.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              C.byref(ms) if timed else None), "gmx_encoder_encode_batch")
+        return ms.value if timed else None
+
+    def encode(self, p, bits, n_bits):
+        """Host arrays p [S][pitch] float32, bits [S][pitch] uint8."""
+        p = np.ascontiguousarray(p, np.float32)
+        bits = np.ascontiguousarray(bits, np.uint8)
+        assert p.ndim == 2 and p.shape == bits.shape and p.shape[0] == self.S
+        n = self._counts(n_bits)
+        check(self.L.gmx_encoder_encode(self.h, _vp(p), _vp(bits), p.shape[1], n.ctypes.data_as(C.POINTER(C.c_uint64))),
+              "gmx_encoder_encode")
+
+    def flush(self, which=None):
+        w = None if which is None else np.ascontiguousarray(np.asarray(which) != 0, np.uint8)
+        assert w is None or w.shape == (self.S,)
+        check(self.L.gmx_encoder_flush(self.h, _vp(w)), "gmx_encoder_flush")
+
+    def take_launch(self):
+        check(self.L.gmx_encoder_take_launch(self.h), "gmx_encoder_take_launch")
+
+    def _taken(self):
+        out = []
+        for s in range(self.S):
+            n = self.L.gmx_encoder_n_bytes(self.h, s)
+            out.append(C.string_at(self.L.gmx_encoder_bytes(self.h, s), n) if n else b"")
+        return out
+
+    def take_wait(self):
+        rc = self.L.gmx_encoder_take_wait(self.h)
+        self.last_taken = self._taken() if rc in (0, -1) else None
+        check(rc, "gmx_encoder_take_wait")   # (a bad p: GmxError, the other streams' bytes are in last_taken)
+        return self.last_taken
+
+    def take(self):
+        """Everything coded since the last take: a list of bytes, one per stream."""
+        self.take_launch()
+        return self.take_wait()
+
+    def total_bytes(self, stream):
+        return int(self.L.gmx_encoder_total_bytes(self.h, stream))
+
+    def bad_bit(self, stream):
+        return int(self.L.gmx_encoder_bad_bit(self.h, stream))
+
+    def d2h_bytes(self):
+        return int(self.L.gmx_debug_encoder_d2h_bytes(self.h))

@@ -24,6 +24,7 @@
 #include "../../include/gmxmix_lstm_group.h"
 #include "../../include/gmxmix_decoder.h"
 #include "../../include/gmxmix_lstm_shape.h"
+#include "../../include/gmxmix_encoder.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
@@ -38,6 +39,7 @@
 #include "gmx_ctx.h"
 #include "gmx_ctx_ckpt.h"
 #include "gmx_coder_dev.h"
+#include "gmx_encoder_dev.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -1558,6 +1560,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 #include "gmx_ctx_ckpt.inc"
 #include "gmx_chainstep.inc"
 #include "gmx_coder.inc"
+#include "gmx_encoder.inc"
 
 // ---- test probes (device math against host math; not part of the product surface) --------
 extern "C" int gmx_debug_single_variant(gmx_group* g, int lanes_per_stream) {
