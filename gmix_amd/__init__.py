@@ -3,12 +3,12 @@ a C ABI (include/gmxmix.h, libgmxmix.so), plus thin host-side mirrors of the ref
 Mixer / Predictor surface for that path.  Nothing here computes on the CPU."""
 from . import topology
 from ._lib import ABI_SYMBOLS, LIB_PATH, GmxError, build
-from .bank import Batch, ChainStep, Encoder, Lockstep, MixerGroup, Topology, device_count
+from .bank import Analysis, Batch, ChainStep, Encoder, Lockstep, MixerGroup, Topology, device_count
 from .indirect import IndirectBatch, IndirectGroup
 from .lstm import LstmBatch, LstmGroup, LstmShape
 from .match import MatchBatch, MatchGroup
 from .ctx import CtxBatch, CtxGroup
 
 __all__ = ["topology", "ABI_SYMBOLS", "LIB_PATH", "GmxError", "build", "Batch", "MixerGroup",
-           "Lockstep", "ChainStep", "Encoder", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch", "LstmShape",
+           "Lockstep", "ChainStep", "Encoder", "Analysis", "Topology", "device_count", "IndirectGroup", "IndirectBatch", "LstmGroup", "LstmBatch", "LstmShape",
            "MatchGroup", "MatchBatch", "CtxGroup", "CtxBatch"]

@@ -334,6 +334,28 @@ def lib():
         L.gmx_encoder_bad_bit.restype = C.c_int64
         L.gmx_debug_encoder_d2h_bytes.argtypes = [vp]
         L.gmx_debug_encoder_d2h_bytes.restype = C.c_int64
+    if hasattr(L, "gmx_analysis_create"):
+        # (include/gmxmix_analysis.h; an older build loaded through GMX_LIB for a comparison lacks them, and a call fails)
+        pu64 = C.POINTER(C.c_uint64)
+        L.gmx_analysis_create.argtypes = [C.POINTER(vp), i32, vp, i32, u64, i32]
+        L.gmx_analysis_destroy.argtypes = [vp]
+        L.gmx_analysis_destroy.restype = None
+        L.gmx_analysis_reset.argtypes = [vp, i32, vp, u64]
+        L.gmx_analysis_set_frequency.argtypes = [vp, i32, u64]
+        L.gmx_analysis_update_batch.argtypes = [vp, vp, pu64, C.POINTER(C.c_float)]
+        L.gmx_analysis_update.argtypes = [vp, vp, vp, u64, pu64]
+        for name in ("take", "take_launch", "take_wait"):
+            getattr(L, "gmx_analysis_" + name).argtypes = [vp]
+        for name in ("ema", "samples", "sample_bits"):
+            f = getattr(L, "gmx_analysis_" + name)
+            f.argtypes = [vp, i32]
+            f.restype = vp
+        for name in ("bits_seen", "n_samples"):
+            f = getattr(L, "gmx_analysis_" + name)
+            f.argtypes = [vp, i32]
+            f.restype = C.c_uint64
+        L.gmx_debug_analysis_d2h_bytes.argtypes = [vp]
+        L.gmx_debug_analysis_d2h_bytes.restype = C.c_int64
     L.gmx_debug_math_probe.argtypes = [i32, vp, vp, u64, i32]
     L.gmx_debug_math_range.argtypes = [i32, u64, u64, i32, C.POINTER(C.c_ulonglong)]
     _LIB = L
@@ -424,4 +446,12 @@ ABI_SYMBOLS_ENCODER = [
     "gmx_encoder_encode", "gmx_encoder_flush", "gmx_encoder_take", "gmx_encoder_take_launch", "gmx_encoder_take_wait",
     "gmx_encoder_bytes", "gmx_encoder_n_bytes", "gmx_encoder_total_bytes", "gmx_encoder_bad_bit",
     "gmx_debug_encoder_d2h_bytes",
+]
+
+# What include/gmxmix_analysis.h declares: the analysis averages on the device.
+ABI_SYMBOLS_ANALYSIS = [
+    "gmx_analysis_create", "gmx_analysis_destroy", "gmx_analysis_reset", "gmx_analysis_set_frequency",
+    "gmx_analysis_update_batch", "gmx_analysis_update", "gmx_analysis_take", "gmx_analysis_take_launch",
+    "gmx_analysis_take_wait", "gmx_analysis_ema", "gmx_analysis_bits_seen", "gmx_analysis_n_samples",
+    "gmx_analysis_samples", "gmx_analysis_sample_bits", "gmx_debug_analysis_d2h_bytes",
 ]

@@ -615,3 +615,92 @@ class Encoder:
 
     def d2h_bytes(self):
         return int(self.L.gmx_debug_encoder_d2h_bytes(self.h))
+
+
+AN_INPUT, AN_MIXER, AN_FINAL_P = 0, 1, 2
+
+
+class Analysis:
+    """The reference's analysis averages (Predictor::RunAnalysis / UpdateEntropy) for S streams x C columns on the device
+    (gmx_analysis, include/gmxmix_analysis.h): updated from a Batch's device arrays, or host arrays; a take returns the
+    averages and the rows of analysis/entropy.tsv captured since the last take."""
+
+    def __init__(self, n_streams, columns, max_samples, device=0):
+        """columns: [(kind, index), ...] with kind AN_INPUT, AN_MIXER or AN_FINAL_P."""
+        self.L = _lib.lib()
+        self.S = int(n_streams)
+        self.columns = [(int(k), int(i)) for k, i in columns]
+        self.C = len(self.columns)
+        cols = np.array(self.columns, np.uint32).reshape(-1, 2)
+        h = C.c_void_p()
+        check(self.L.gmx_analysis_create(C.byref(h), self.S, _vp(cols), self.C, int(max_samples), device),
+              "gmx_analysis_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gmx_analysis_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _counts(self, n_bits):
+        n = np.full(self.S, n_bits, np.uint64) if np.isscalar(n_bits) else np.ascontiguousarray(n_bits, np.uint64)
+        assert n.shape == (self.S,)
+        return n
+
+    def reset(self, stream=-1, ema=None, bits_seen=0):
+        """stream -1: all.  ema None: zeros; otherwise the C averages of a checkpoint."""
+        e = None if ema is None else np.ascontiguousarray(ema, np.float64)
+        assert e is None or e.shape == (self.C,)
+        check(self.L.gmx_analysis_reset(self.h, stream, _vp(e), int(bits_seen)), "gmx_analysis_reset")
+
+    def set_frequency(self, frequency, stream=-1):
+        check(self.L.gmx_analysis_set_frequency(self.h, stream, int(frequency)), "gmx_analysis_set_frequency")
+
+    def update_batch(self, batch, n_bits, timed=False):
+        """Bits [0, n_bits[s]) of every stream from the batch's device arrays (an int: every stream)."""
+        n = self._counts(n_bits)
+        ms = C.c_float(0)
+        check(self.L.gmx_analysis_update_batch(self.h, batch.h, n.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               C.byref(ms) if timed else None), "gmx_analysis_update_batch")
+        return ms.value if timed else None
+
+    def update(self, values, bits, n_bits):
+        """Host arrays values [S][pitch][C] float32 (a logit per column, a probability for AN_FINAL_P), bits [S][pitch]."""
+        values = np.ascontiguousarray(values, np.float32)
+        bits = np.ascontiguousarray(bits, np.uint8)
+        assert values.ndim == 3 and values.shape == bits.shape + (self.C,) and bits.shape[0] == self.S
+        n = self._counts(n_bits)
+        check(self.L.gmx_analysis_update(self.h, _vp(values), _vp(bits), bits.shape[1],
+                                         n.ctypes.data_as(C.POINTER(C.c_uint64))), "gmx_analysis_update")
+
+    def take_launch(self):
+        check(self.L.gmx_analysis_take_launch(self.h), "gmx_analysis_take_launch")
+
+    def take_wait(self):
+        """[(ema [C] float64, bits_seen, rows [k][C] float64, labels [k] uint64)] per stream (copies)."""
+        check(self.L.gmx_analysis_take_wait(self.h), "gmx_analysis_take_wait")
+        out = []
+        for s in range(self.S):
+            k = int(self.L.gmx_analysis_n_samples(self.h, s))
+            ema = np.frombuffer(C.string_at(self.L.gmx_analysis_ema(self.h, s), 8 * self.C), np.float64)
+            rows = np.zeros((0, self.C), np.float64)
+            labels = np.zeros(0, np.uint64)
+            if k:
+                rows = np.frombuffer(C.string_at(self.L.gmx_analysis_samples(self.h, s), 8 * self.C * k),
+                                     np.float64).reshape(k, self.C)
+                labels = np.frombuffer(C.string_at(self.L.gmx_analysis_sample_bits(self.h, s), 8 * k), np.uint64)
+            out.append((ema, int(self.L.gmx_analysis_bits_seen(self.h, s)), rows, labels))
+        return out
+
+    def take(self):
+        self.take_launch()
+        return self.take_wait()
+
+    def d2h_bytes(self):
+        return int(self.L.gmx_debug_analysis_d2h_bytes(self.h))
