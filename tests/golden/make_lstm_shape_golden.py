@@ -11,7 +11,8 @@ how often each of the three ClipGradients calls moved an element and how many ba
 must clip at least once in state_error_ and in stored_error_; were that not so for its seed, another seed is chosen
 HERE (synth seed 13 was, after 6 did not clip).  The third call, ClipGradients(hidden_error), can never move an element
 of a one-layer model: LstmLayer::BackwardPass sets *hidden_error = 0 before it and only `layer > 0` adds to it, so its
-counter is recorded as the 0 it must be.
+counter is recorded as the 0 it must be.  The `hot*` cases must reach exact-zero softmax outputs, silent bits and clips in
+both arrays on the restatement, or the script stops.
 """
 import argparse
 import os
@@ -34,6 +35,10 @@ CASES = [
     ("lowclip", (65, 7, 0.01, 0.05), 30, 12, 13, 255, 1),
     ("stock", (50, 100, 0.03, 10.0), 330, 0xDEADBEEF, 7, 255, 0),
     ("wide", (130, 5, 0.05, 10.0), 17, 14, 8, 63, 0),
+    # the hard regimes, reached through learning_rate and gradient_clip alone: softmax outputs exactly 0, silent bits,
+    # predictions at the logit clamp, hundreds of clipped elements (lstm_shape_common.regime_evidence counts them)
+    ("hot255", (255, 9, 30.0, 0.05), 46, 5, 77, 255, 1),
+    ("hot7", (7, 33, 100.0, 0.001), 200, 5, 77, 255, 1),
 ]
 
 TUS = ["models/lstm.cpp", "models/lstm-layer.cpp", "memory/long-term-memory.cpp", "memory/short-term-memory.cpp",
@@ -77,6 +82,10 @@ def main():
             if name == "lowclip":
                 assert min(clips[:2]) >= 1, ("choose another seed", clips)
             assert clips[2] == 0, (name, clips)
+            if name.startswith("hot"):   # a hot case that is not hot pins nothing: choose another shape or seed HERE
+                ev = lsc.regime_evidence(r, got)
+                assert ev["nan"] == 0, (name, ev)
+                assert ev["zero_probs"] > 0 and ev["silent_bits"] > 0 and min(clips[:2]) >= 1, (name, ev)
             names.append(name)
             rec = dict(cells=np.int32(cells), horizon=np.int32(horizon), lr=np.float32(shape[2]), clip=np.float32(shape[3]),
                        seed=np.uint32(seed), synth_seed=np.uint32(sseed), mask=np.uint32(mask), family=np.uint32(family),

@@ -126,12 +126,121 @@ class Ref:
     def backward_passes(self):
         return int(self.L.lsr_backward_passes(self.p))
 
+    def update_steps(self):
+        """LstmLayer::update_steps_: Adam's step count, which stops at update_limit 3000."""
+        return int(self.L.lsr_update_steps(self.p))
+
     def memory_usage(self):
         return int(self.L.lsr_memory_usage(self.p))
 
 
 def u32(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# ---- the hard regimes and the corners of the advertised range (tests/test_lstm_shape_census.py counts them on the CPU,
+# tests/test_gpu_lstm_shape_regimes.py recounts and then looks at the general kernel) ----------------------------------
+_CLAMP = np.float32(np.log(np.float32(np.float32(0.9999) / (np.float32(1) - np.float32(0.9999)))))
+
+
+def regime_evidence(ref, out):
+    """What the restatement alone says about a run: `out` is what ref.run() returned, the counters are ref's (they
+    count from its creation).  zero_probs, silent_bits and clamped_logits as goldenlib.lstm_regime_evidence defines them:
+    softmax outputs exactly 0.0f; bits where the model stayed silent (denom == 0: not active, the previous prediction
+    repeated and not the 0 an inactive p == 0.5 stores); predictions at +-logit(0.9999f).  clips: Ref.clip_counts().
+    nan: NaNs among the distributions, the gate weights and the output layer -- a row that reaches one pins nothing."""
+    flat, fact = out["pred"].reshape(-1), out["act"].reshape(-1)
+    prev = np.concatenate([[np.float32(0)], flat[:-1]])
+    silent = int(((fact == 0) & (u32(flat) == u32(prev)) & (flat != 0)).sum())
+    nan = int(np.isnan(out["probs"]).sum() + np.isnan(ref.weights()).sum() + np.isnan(ref.output_layer()).sum())
+    return dict(zero_probs=int((out["probs"] == 0.0).sum()), silent_bits=silent,
+                clamped_logits=int((np.abs(flat) >= _CLAMP).sum()), clips=ref.clip_counts(),
+                backward_passes=ref.backward_passes(), update_steps=ref.update_steps(), nan=nan)
+
+
+def assert_needs(row, s, ev):
+    """The counts a row exists for are there (on the stream `on` that reaches them), and no stream met a NaN."""
+    assert ev["nan"] == 0, (row["shape"], s, ev)
+    if s != row.get("on", s):
+        return
+    for k in row["needs"]:
+        v = min(ev[k][:2]) if k == "clips" else ev[k]      # clips: in state_error_ and in stored_error_
+        assert v > 0, (row["shape"], s, k, ev)
+
+
+# Shaped banks, three launches by chunks_for (at horizon 256 and 513 bytes these are 255, 257 and 1 bytes).  Stream s has
+# gate weights of seed `wseed` + s and the inputs make_streams(seed = `seed`) gives it: stream 1 is the sparse / one-hot
+# family, where the hot shapes reach their regimes.  lin = 257 + cells, hid = cells + 1, cp = cells rounded up to 64.
+CORNER_ROWS = [
+    # lin 320 and hid 64 fill their 64-float pitches; 10 passes
+    dict(shape=(63, 4, 8.0, 0.5), S=3, N=41, needs=("clips", "clamped_logits"), on=1),
+    # lin 512 and hid 256 fill theirs
+    dict(shape=(255, 9, 30.0, 0.05), S=3, N=46, needs=("zero_probs", "silent_bits", "clamped_logits", "clips"), on=1),
+    # cp exactly 128
+    dict(shape=(128, 3, 0.03, 10.0), S=3, N=10, needs=()),
+    # odd horizon, tiny clip, huge rate
+    dict(shape=(7, 33, 100.0, 0.001), S=3, N=200, needs=("zero_probs", "silent_bits", "clamped_logits", "clips"), on=1),
+    # the horizon maximum with one cell
+    dict(shape=(1, 256, 0.03, 10.0), S=3, N=769, needs=()),
+    # cp 192 (576 items), the horizon maximum
+    dict(shape=(192, 256, 4.0, 0.2), S=2, N=513, needs=("clips", "clamped_logits"), on=1),
+    # both maxima: the largest bank
+    dict(shape=(256, 256, 0.03, 10.0), S=2, N=513, needs=("clips",), on=0),
+]
+for _r in CORNER_ROWS:
+    _r.setdefault("seed", 76)
+    _r.setdefault("wseed", 4)
+
+# One ragged launch, then learning on, off across two horizon boundaries, and on again
+SWITCH_ROW = dict(shape=(63, 4, 8.0, 0.5), S=3, ragged=[0, 3, 9], schedule=[(14, True), (7, False), (20, True)],
+                  seed=76, wseed=4, needs=("clips", "clamped_logits"), on=1)
+
+# Many backward passes in one launch, and Adam's step count at update_limit 3000: two streams over the SAME 6101 bytes
+# (synth seed 77), stream 1 with other gate weights and its launches one byte off stream 0's, so that its passes fall at
+# other rows of the launch's Adam table.  The first launch holds 2000 passes, the 3000th falls inside the second.
+LIMIT_BYTES, LIMIT_LAUNCHES = 6101, [[4001, 2050, 50], [4000, 2050, 51]]
+LIMIT_ROWS = [
+    dict(shape=(3, 2, 0.03, 10.0), family=0, seed=77, wseed=5, needs=(), passes=3050, steps=3000),
+    dict(shape=(2, 2, 2.0, 1.0), family=1, seed=77, wseed=5, needs=("clips", "clamped_logits"), passes=3050, steps=3000),
+]
+
+
+def limit_inputs(gmxo, row):
+    """(ppm, data) of LIMIT_BYTES bytes, and of the 10 bytes that follow the export / import."""
+    return (gmxo.lstm_synth(LIMIT_BYTES, seed=row["seed"], mask=255, family=row["family"]),
+            gmxo.lstm_synth(10, seed=row["seed"] + 1, mask=255, family=row["family"]))
+
+
+def run_refs(row, streams):
+    """[(Ref, its initial gate weights, what its run() over the stream's whole input returned)]: stream s draws its
+    weights from seed row["wseed"] + s."""
+    refs = []
+    for s, (ppm, data) in enumerate(streams):
+        r = Ref(row["shape"], seed=row["wseed"] + s)
+        w0 = r.weights()
+        refs.append((r, w0, r.run(ppm, data)))
+    return refs
+
+
+def switch_evidence(row, streams):
+    """SWITCH_ROW on the restatement alone: [regime_evidence over the ragged launch and the whole schedule] per stream;
+    a stretch without Learn runs no backward pass."""
+    evs = []
+    for s, (ppm, data) in enumerate(streams):
+        r = Ref(row["shape"], seed=row["wseed"] + s)
+        pos = row["ragged"][s]
+        outs = [r.run(ppm[:pos], data[:pos])]
+        for n, learn in row["schedule"]:
+            before = r.backward_passes()
+            outs.append(r.run(ppm[pos:pos + n], data[pos:pos + n], learn=learn))
+            assert learn or r.backward_passes() == before
+            pos += n
+        evs.append(regime_evidence(r, {k: np.concatenate([o[k] for o in outs]) for k in outs[0]}))
+    return evs
+
+
+# The stock kernel's fixtures (tests/golden/cases.py) replayed on a stock-shape bank of the general layout
+ANY_FIXTURES = ["lstm_saturated", "lstm_onehot", "lstm_clipped", "lstm_short"]
 
 
 def sha(b):

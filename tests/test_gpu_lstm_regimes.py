@@ -73,9 +73,11 @@ def _harness_checksum(oracle, P, A, Cx):
     return oracle.fnv64_bytes(rec.reshape(-1))
 
 
-@pytest.mark.parametrize("name", sorted(LSTM_REGIMES))
-def test_lstm_kernel_in_hard_regimes(gpu, oracle, name, lstm_build):
-    _assert_regime_reached(oracle, name)
+def replay_fixture_in_chunks(gpu, oracle, name):
+    """A fixture of tests/golden/cases.py from its starting state through the batched kernel in launches of 120 bytes,
+    against the oracle and against the reference's own run.  The bank is created HERE: under GMX_LSTM_BUILD=any
+    (tests/test_gpu_lstm_shape_regimes.py) it has the general layout and kernel.  Returns (launches, what
+    gmx_debug_lstm_any_launches counted)."""
     meta, z = goldenlib.load(name)
     kw, N, D = meta["synth"], meta["bytes"], meta["dump"]
     ppm, data = oracle.lstm_synth(N, seed=kw.get("seed", 0), mask=kw.get("mask", 255), family=kw.get("family", 0))
@@ -97,22 +99,29 @@ def test_lstm_kernel_in_hard_regimes(gpu, oracle, name, lstm_build):
     assert _harness_checksum(oracle, P[0], A[0], Cx[0]) == meta["h64"]
     assert len(sh) == meta["short_size"] and oracle.fnv64_bytes(sh) == meta["short_hash"]
     assert oracle.fnv64_bytes(lng) == meta["long_hash"]
+    counted = g.any_launches
     g.close()
+    return (N + 119) // 120, counted
 
 
-def test_lstm_session_in_saturated_regime(gpu, oracle):
-    """lstm_saturated one byte at a time through the persistent session (gmx_lstm_forward / gmx_lstm_perceive: the
-    <154, 2, true> instantiation, another launch shape around the same code): the byte distributions with their exact
-    zeros against the oracle's, the bits coded from them on the host against the reference's dump, two backward
-    passes, the files at the end."""
-    name = "lstm_saturated"
+@pytest.mark.parametrize("name", sorted(LSTM_REGIMES))
+def test_lstm_kernel_in_hard_regimes(gpu, oracle, name, lstm_build):
     _assert_regime_reached(oracle, name)
+    replay_fixture_in_chunks(gpu, oracle, name)
+
+
+def replay_saturated_per_byte(gpu, oracle, sessions):
+    """lstm_saturated one byte at a time through gmx_lstm_forward / gmx_lstm_perceive; sessions: through the persistent
+    session, else as the bank itself decides (a bank of the general layout launches its kernel at every call).  Returns
+    (calls, what gmx_debug_lstm_any_launches counted)."""
+    name = "lstm_saturated"
     meta, z = goldenlib.load(name)
     kw, N = meta["synth"], 230
     ppm, data = oracle.lstm_synth(N, seed=kw.get("seed", 0), mask=kw.get("mask", 255), family=kw.get("family", 0))
     m, g = _start(gpu, oracle, kw)
-    g.L.gmx_debug_lstm_use_sessions.argtypes = [C.c_void_p, C.c_int]
-    assert g.L.gmx_debug_lstm_use_sessions(g.h, 1) == 0
+    if sessions:
+        g.L.gmx_debug_lstm_use_sessions.argtypes = [C.c_void_p, C.c_int]
+        assert g.L.gmx_debug_lstm_use_sessions(g.h, 1) == 0
     last, zeros = 0, 0
     for n in range(N):
         probs, ctx = g.forward(ppm[n], last)
@@ -129,7 +138,18 @@ def test_lstm_session_in_saturated_regime(gpu, oracle):
     # (where a byte has ended the bank writes the range of its eighth bit; the oracle's byte-level calls never coded
     # the bits, its range is still the forward's: the first 12 bytes)
     assert lng == m.export_long() and sh[12:] == m.export_short()[12:]
+    counted = g.any_launches
     g.close()
+    return 2 * N, counted
+
+
+def test_lstm_session_in_saturated_regime(gpu, oracle):
+    """lstm_saturated one byte at a time through the persistent session (gmx_lstm_forward / gmx_lstm_perceive: the
+    <154, 2, true> instantiation, another launch shape around the same code): the byte distributions with their exact
+    zeros against the oracle's, the bits coded from them on the host against the reference's dump, two backward
+    passes, the files at the end."""
+    _assert_regime_reached(oracle, "lstm_saturated")
+    replay_saturated_per_byte(gpu, oracle, sessions=True)
 
 
 @pytest.mark.parametrize("over", [45, 0], ids=["above_the_cu_count", "at_the_cu_count"])

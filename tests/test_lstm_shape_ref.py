@@ -1,5 +1,5 @@
 """tests/lstm_shape_ref.c -- the LSTM byte model at any shape, what the shaped device banks are compared with -- pinned
-on the CPU: to oracle.LstmModel at the stock shape, and to the reference's own Lstm class at four shapes through
+on the CPU: to oracle.LstmModel at the stock shape, and to the reference's own Lstm class at six shapes, two of them in the hard regimes, through
 tests/golden/lstm_shapes.npz (tests/golden/make_lstm_shape_golden.py).  Tolerance 0: floats are compared as uint32."""
 import numpy as np
 import pytest
@@ -39,6 +39,29 @@ def test_restatement_equals_oracle_at_the_stock_shape():
         assert r.export_long() == o.export_long(), (a, ".long")
         assert r.export_short() == o.export_short(), (a, ".short")
     assert r.backward_passes() == 2
+
+
+def test_learning_switched_off_and_on_again_equals_oracle_at_the_stock_shape():
+    """Learn on for 130 bytes, off for 210 (Predict alone takes epoch_ across the wraps at bytes 200 and 300: output
+    layers no Perceive refreshes, no backward pass), on again for 180: the first Perceive after the gap finds an
+    input_history_ and a ring that were filled without it, and the backward pass at byte 400 runs over epochs forwarded
+    while Learn was off."""
+    ppm, data = gmxo.lstm_synth(520, seed=23, mask=63, family=0)
+    o = gmxo.LstmModel(SEED)
+    r = lsc.Ref(lsc.STOCK, seed=SEED)
+    passes = []
+    for a, b, learn in ((0, 130, True), (130, 340, False), (340, 520, True)):
+        pred, act, ctx = o.run(ppm[a:b], data[a:b], learn=learn)
+        got = r.run(ppm[a:b], data[a:b], learn=learn)
+        assert np.array_equal(u32(got["pred"]), u32(pred)), (a, "bit predictions")
+        assert np.array_equal(got["act"], act), (a, "active flags")
+        assert np.array_equal(got["ctx"], ctx), (a, "contexts")
+        assert np.array_equal(u32(r.weights()), u32(o.weights())), (a, "gate weights")
+        assert np.array_equal(u32(r.output_layer()), u32(o.output_layer())), (a, "output layer")
+        assert r.export_long() == o.export_long(), (a, ".long")
+        assert r.export_short() == o.export_short(), (a, ".short")
+        passes.append(r.backward_passes())
+    assert passes == [1, 1, 3] and r.update_steps() == 3
 
 
 @pytest.mark.parametrize("case", lsc.golden(), ids=lambda c: c["name"])
