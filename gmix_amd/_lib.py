@@ -356,6 +356,42 @@ def lib():
             f.restype = C.c_uint64
         L.gmx_debug_analysis_d2h_bytes.argtypes = [vp]
         L.gmx_debug_analysis_d2h_bytes.restype = C.c_int64
+    if hasattr(L, "gmx_ppmd_create"):
+        # (include/gmxmix_ppmd.h; an older build loaded through GMX_LIB for a comparison lacks them, and a call fails)
+        L.gmx_ppmd_create.argtypes = [C.POINTER(vp), i32, i32, i32, i32]
+        L.gmx_ppmd_destroy.argtypes = [vp]
+        L.gmx_ppmd_destroy.restype = None
+        L.gmx_ppmd_n_streams.argtypes = [vp]
+        L.gmx_ppmd_bank_bytes.argtypes = [vp]
+        L.gmx_ppmd_bank_bytes.restype = u64
+        L.gmx_ppmd_reset.argtypes = [vp, i32]
+        L.gmx_ppmd_sync.argtypes = [vp]
+        L.gmx_ppmd_batch_create.argtypes = [C.POINTER(vp), vp, u64]
+        L.gmx_ppmd_batch_destroy.argtypes = [vp]
+        L.gmx_ppmd_batch_destroy.restype = None
+        L.gmx_ppmd_batch_max_bytes.argtypes = [vp]
+        L.gmx_ppmd_batch_max_bytes.restype = u64
+        for name in ("bytes", "ppm", "predictions", "active", "used"):
+            f = getattr(L, "gmx_ppmd_batch_" + name)
+            f.argtypes = [vp]
+            f.restype = vp
+        L.gmx_ppmd_batch_upload.argtypes = [vp, u64]
+        L.gmx_ppmd_batch_download.argtypes = [vp, u64, C.c_uint]
+        L.gmx_ppmd_batch_wait.argtypes = [vp]
+        L.gmx_ppmd_run.argtypes = [vp, vp, u64, C.POINTER(C.c_float)]
+        L.gmx_ppmd_run_ragged.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+        L.gmx_ppmd_feed.argtypes = [vp, vp, u64, vp, vp, i32]
+        L.gmx_ppmd_step_launch.argtypes = [vp, vp, vp]
+        L.gmx_ppmd_step_wait.argtypes = [vp]
+        L.gmx_ppmd_step.argtypes = [vp, vp, vp]
+        L.gmx_ppmd_step_ppm.argtypes = [vp]
+        L.gmx_ppmd_step_ppm.restype = vp
+        L.gmx_ppmd_memory_usage.argtypes = [vp, i32]
+        L.gmx_ppmd_memory_usage.restype = u64
+        L.gmx_ppmd_restores.argtypes = [vp, i32]
+        L.gmx_ppmd_restores.restype = C.c_int64
+        L.gmx_debug_ppmd_launches.argtypes = [vp]
+        L.gmx_debug_ppmd_launches.restype = C.c_int64
     L.gmx_debug_math_probe.argtypes = [i32, vp, vp, u64, i32]
     L.gmx_debug_math_range.argtypes = [i32, u64, u64, i32, C.POINTER(C.c_ulonglong)]
     _LIB = L
@@ -454,4 +490,14 @@ ABI_SYMBOLS_ANALYSIS = [
     "gmx_analysis_update_batch", "gmx_analysis_update", "gmx_analysis_take", "gmx_analysis_take_launch",
     "gmx_analysis_take_wait", "gmx_analysis_ema", "gmx_analysis_bits_seen", "gmx_analysis_n_samples",
     "gmx_analysis_samples", "gmx_analysis_sample_bits", "gmx_debug_analysis_d2h_bytes",
+]
+
+# What include/gmxmix_ppmd.h declares: the PPMd byte model on the device.
+ABI_SYMBOLS_PPMD = [
+    "gmx_ppmd_create", "gmx_ppmd_destroy", "gmx_ppmd_n_streams", "gmx_ppmd_bank_bytes", "gmx_ppmd_reset", "gmx_ppmd_sync",
+    "gmx_ppmd_batch_create", "gmx_ppmd_batch_destroy", "gmx_ppmd_batch_max_bytes", "gmx_ppmd_batch_bytes",
+    "gmx_ppmd_batch_ppm", "gmx_ppmd_batch_predictions", "gmx_ppmd_batch_active", "gmx_ppmd_batch_used",
+    "gmx_ppmd_batch_upload", "gmx_ppmd_batch_download", "gmx_ppmd_batch_wait", "gmx_ppmd_run", "gmx_ppmd_run_ragged",
+    "gmx_ppmd_feed", "gmx_ppmd_step_launch", "gmx_ppmd_step_wait", "gmx_ppmd_step", "gmx_ppmd_step_ppm",
+    "gmx_ppmd_memory_usage", "gmx_ppmd_restores", "gmx_debug_ppmd_launches",
 ]

@@ -704,3 +704,144 @@ class Analysis:
 
     def d2h_bytes(self):
         return int(self.L.gmx_debug_analysis_d2h_bytes(self.h))
+
+
+PPMD_PPM, PPMD_PREDICTIONS, PPMD_USED, PPMD_ALL = 1, 2, 4, 7
+
+
+class PpmdGroup:
+    """The reference's PPMD::ModPPMD for S streams on the device (gmx_ppmd, include/gmxmix_ppmd.h): per byte the
+    normalised byte distribution, the model's eight bit predictions and its memory usage."""
+
+    def __init__(self, n_streams, order=20, arena_mb=64, device=0):
+        self.L = _lib.lib()
+        self.S, self.order, self.arena_mb = int(n_streams), int(order), int(arena_mb)
+        h = C.c_void_p()
+        check(self.L.gmx_ppmd_create(C.byref(h), self.S, self.order, self.arena_mb, device), "gmx_ppmd_create")
+        self.h = h
+        ptr = self.L.gmx_ppmd_step_ppm(self.h)
+        buf = (C.c_byte * (self.S * 1024)).from_address(ptr)
+        self.step_ppm = np.frombuffer(buf, dtype=np.float32).reshape(self.S, 256)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.step_ppm = None
+            self.L.gmx_ppmd_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def bank_bytes(self):
+        return int(self.L.gmx_ppmd_bank_bytes(self.h))
+
+    def reset(self, stream=-1):
+        check(self.L.gmx_ppmd_reset(self.h, stream), "gmx_ppmd_reset")
+
+    def sync(self):
+        check(self.L.gmx_ppmd_sync(self.h), "gmx_ppmd_sync")
+
+    def run(self, batch, n_bytes=None, timed=False):
+        """The first n_bytes records of every stream; an array: n_bytes[s] of stream s (0 sits the call out)."""
+        if n_bytes is None:
+            n_bytes = batch.max_bytes
+        if np.isscalar(n_bytes):
+            ms = C.c_float(0)
+            check(self.L.gmx_ppmd_run(self.h, batch.h, int(n_bytes), C.byref(ms) if timed else None), "gmx_ppmd_run")
+            return ms.value if timed else None
+        n = np.ascontiguousarray(n_bytes, np.uint64)
+        assert n.shape == (self.S,)
+        check(self.L.gmx_ppmd_run_ragged(self.h, batch.h, n.ctypes.data_as(C.POINTER(C.c_uint64))), "gmx_ppmd_run_ragged")
+        return None
+
+    def feed(self, batch, n_bytes, lstm_batch=None, mixer_batch=None, slot=0):
+        check(self.L.gmx_ppmd_feed(self.h, batch.h, int(n_bytes), lstm_batch.h if lstm_batch is not None else None,
+                                   mixer_batch.h if mixer_batch is not None else None, int(slot)), "gmx_ppmd_feed")
+
+    def step_launch(self, last_byte, take=None):
+        last = np.ascontiguousarray(last_byte, np.uint8)
+        take = np.ones(self.S, np.uint8) if take is None else np.ascontiguousarray(take, np.uint8)
+        assert last.shape == take.shape == (self.S,)
+        check(self.L.gmx_ppmd_step_launch(self.h, _vp(last), _vp(take)), "gmx_ppmd_step_launch")
+
+    def step_wait(self):
+        check(self.L.gmx_ppmd_step_wait(self.h), "gmx_ppmd_step_wait")
+        return self.step_ppm
+
+    def step(self, last_byte, take=None):
+        """UpdateByte(last_byte[s]) and PrepareByte of every stream with take[s] != 0 -> ppm [S][256] (the bank's pinned
+        array: a view, overwritten by the next step)."""
+        self.step_launch(last_byte, take)
+        return self.step_wait()
+
+    def memory_usage(self, stream):
+        return int(self.L.gmx_ppmd_memory_usage(self.h, stream))
+
+    def restores(self, stream):
+        return int(self.L.gmx_ppmd_restores(self.h, stream))
+
+    def launches(self):
+        return int(self.L.gmx_debug_ppmd_launches(self.h))
+
+
+class PpmdBatch:
+    def __init__(self, group, max_bytes):
+        self.g = group
+        self.L = group.L
+        self.max_bytes = int(max_bytes)
+        h = C.c_void_p()
+        check(self.L.gmx_ppmd_batch_create(C.byref(h), group.h, self.max_bytes), "gmx_ppmd_batch_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gmx_ppmd_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _view(self, fn, dtype, shape):
+        ptr = fn(self.h)
+        if not ptr:
+            raise GmxError(-2, fn.__name__)
+        n = int(np.prod(shape))
+        buf = (C.c_byte * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+        return np.frombuffer(buf, dtype=dtype).reshape(shape)
+
+    @property
+    def bytes(self):
+        return self._view(self.L.gmx_ppmd_batch_bytes, np.uint8, (self.g.S, self.max_bytes))
+
+    @property
+    def ppm(self):
+        return self._view(self.L.gmx_ppmd_batch_ppm, np.float32, (self.g.S, self.max_bytes, 256))
+
+    @property
+    def predictions(self):
+        return self._view(self.L.gmx_ppmd_batch_predictions, np.float32, (self.g.S, self.max_bytes, 8))
+
+    @property
+    def active(self):
+        return self._view(self.L.gmx_ppmd_batch_active, np.uint8, (self.g.S, self.max_bytes, 8))
+
+    @property
+    def used(self):
+        return self._view(self.L.gmx_ppmd_batch_used, np.uint64, (self.g.S, self.max_bytes))
+
+    def upload(self, n_bytes=None):
+        check(self.L.gmx_ppmd_batch_upload(self.h, self.max_bytes if n_bytes is None else n_bytes), "gmx_ppmd_batch_upload")
+
+    def download(self, n_bytes=None, what=PPMD_ALL):
+        check(self.L.gmx_ppmd_batch_download(self.h, self.max_bytes if n_bytes is None else n_bytes, what),
+              "gmx_ppmd_batch_download")
+
+    def wait(self):
+        check(self.L.gmx_ppmd_batch_wait(self.h), "gmx_ppmd_batch_wait")

@@ -1,5 +1,5 @@
-// gmx_batch_rows.h -- what the record batches of the five bank types (mixers, Indirect models, LSTM, Match models,
-// context variables) have in common, as far as it needs no HIP: the geometry of a transfer of the first records of
+// gmx_batch_rows.h -- what the record batches of the six bank types (mixers, Indirect models, LSTM, Match models,
+// context variables, PPMd) have in common, as far as it needs no HIP: the geometry of a transfer of the first records of
 // every stream, and the table of a batch's columns with the declarations of the five tables.  The transfers
 // themselves, their streams and their ordering are GmxBatchCore's in gmx_capi.cpp; a plain host program can drive
 // what is here (tests/cpp/test_batch_rows.cpp).
@@ -121,6 +121,17 @@ static inline void gmx_ctx_batch_cols(GmxBatchCols& t, B* b, int v, unsigned fla
   t.add(&b->d_bits, &b->h_bits, 1, GMX_COL_UP);
   if (flags & GMX_CTX_BATCH_VALUES) t.add(&b->d_values, &b->h_values, (size_t)v * 4, GMX_COL_DOWN);
   t.add_device_only(&b->d_scratch);  // [S][max_fires][H], made by gmx_ctx_batch_create
+}
+
+// The PPMd bank's records are bytes: the byte in; its distribution, the eight bit predictions with their flags and the
+// model's memory usage out.
+template <class B>
+static inline void gmx_ppmd_batch_cols(GmxBatchCols& t, B* b) {
+  t.add(&b->d_bytes, &b->h_bytes, 1, GMX_COL_UP);
+  t.add(&b->d_ppm, &b->h_ppm, 256 * 4, GMX_COL_DOWN);
+  t.add(&b->d_pred, &b->h_pred, 8 * 4, GMX_COL_DOWN);
+  t.add(&b->d_act, &b->h_act, 8, GMX_COL_DOWN);
+  t.add(&b->d_used, &b->h_used, 8, GMX_COL_DOWN);
 }
 
 #endif  // GMX_BATCH_ROWS_H_

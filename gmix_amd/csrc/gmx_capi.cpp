@@ -26,6 +26,7 @@
 #include "../../include/gmxmix_lstm_shape.h"
 #include "../../include/gmxmix_encoder.h"
 #include "../../include/gmxmix_analysis.h"
+#include "../../include/gmxmix_ppmd.h"
 #include "gmx_buildhash.h"
 #include "gmx_internal.h"
 #include "gmx_mailbox.h"
@@ -42,6 +43,7 @@
 #include "gmx_coder_dev.h"
 #include "gmx_encoder_dev.h"
 #include "gmx_analysis_dev.h"
+#include "gmx_ppmd_dev.h"
 
 struct GmxSynthArgs {
   float* pred;
@@ -1564,6 +1566,7 @@ extern "C" int gmx_bank_memory_usage(gmx_group* g, int stream, int mixer, uint64
 #include "gmx_coder.inc"
 #include "gmx_encoder.inc"
 #include "gmx_analysis.inc"
+#include "gmx_ppmd.inc"
 
 // ---- test probes (device math against host math; not part of the product surface) --------
 extern "C" int gmx_debug_single_variant(gmx_group* g, int lanes_per_stream) {
